@@ -13,9 +13,16 @@ One step = one pass of the hot path over one batch of synthetic input, all on th
 Weak scaling (default): every rank processes B walks per step; `--scaling strong`: the global
 batch is B walks and every rank trains 1/N of it. `value` = positive pairs of ALL ranks / s.
 
-Also reported: walks/s of the walker alone (DeepWalk and node2vec p=.25 q=4), the SGNS kernel
-against the HBM roofline (algorithmic bytes / live HIP-event kernel time), and the CPU
-baseline (the oracle = reference-algorithm restatement, rank 0 at N=1, bounded sample).
+A plain run sets up, warms up, times the --steps steps and prints the JSON line (`value`,
+`ms_per_step`, the step's roofline from its own HIP events). `--dump-outputs DIR` then also
+writes what the last timed step left (DIR/*.npy, see dump_outputs): the inputs are the same from
+run to run, so two builds can be compared output for output.
+
+With `--full` also reported, each from runs of its own after the timed steps: the measured copy
+roofline, the same step with the bit-exact walker, walks/s of the walker alone (DeepWalk and
+node2vec p=.25 q=4) with their rooflines, the 64-walk batch line (`batch64`), the C5 line (`c5`),
+the N > 1 lines' checked step, and the CPU baseline (the oracle = reference-algorithm
+restatement, rank 0 at N=1, bounded sample).
 """
 import argparse
 import json
@@ -108,6 +115,34 @@ def dependent_line_roofline(steps: int, kern_s: float, lines_per_step: float, ta
             'gather_lines_per_s': rate['gather_lines_per_s'],
             'frac_of_chase': lines_s / rate['chase_lines_per_s'],
             'lines': what, 'source': rate['source']}
+
+
+def dump_outputs(path: str, tables, owner: bool, walks: torch.Tensor, loss_acc: torch.Tensor):
+    """--dump-outputs: what the timed steps left after the last of them, as ``path``/<name>.npy
+    (about 40 MB at most):
+      rows_in, w_in     a fixed, seeded sample of in-table rows (sorted ids, float64) and those
+                        rows of the in table (float32), every deferred lazy update applied;
+      rows_out, w_out   the same for the out table (owner layout at N > 1: the sampled rows this
+                        rank owns);
+      walks             the last step's walks (node ids as float64; the first walks of a large
+                        batch);
+      loss_terms        the float64 loss accumulators of the timed steps."""
+    os.makedirs(path, exist_ok=True)
+    V, d = tables.V, tables.d
+    n = min(V, (16 << 20) // (4 * d))
+    rows = np.sort(np.random.default_rng(0).choice(V, size=n, replace=False))
+    idx = torch.from_numpy(rows).to(walks.device)
+    w_in = tables.w_in[idx]                   # (the lazy tables flush both tables here)
+    if owner:                                 # local row j of rank r is global row r + world * j
+        idx_out = idx[idx % tables.world == tables.rank]
+        w_out = tables.w_out[idx_out // tables.world]
+    else:
+        idx_out, w_out = idx, tables.w_out[idx]
+    n_w = min(walks.shape[0], max(1, (8 << 20) // (8 * walks.shape[1])))
+    out = {'rows_in': idx.double(), 'w_in': w_in.float(), 'rows_out': idx_out.double(),
+           'w_out': w_out.float(), 'walks': walks[:n_w].double(), 'loss_terms': loss_acc.double()}
+    for name, t in out.items():
+        np.save(os.path.join(path, name + '.npy'), t.cpu().numpy())
 
 
 _RESULT = {}   # run()'s JSON line, printed by main()
@@ -564,6 +599,16 @@ def main():
     ap.add_argument('--steps', type=int, default=400,
                     help='timed steps (C3: ~2.7 s of GPU time, so the job clock sees the GPU busy)')
     ap.add_argument('--warmup', type=int, default=10)
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run everything else the benchmark measures '
+                         'or checks (the copy roofline, the exact-walk steps, the walkers alone, '
+                         'batch64, c5, the N > 1 step check, the CPU baseline; each still has its '
+                         'own switch below). Without it only the headline steps are run and '
+                         'those parts of the line are null or absent')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps write what they left as DIR/<name>.npy: a '
+                         'seeded sample of rows of both tables, the last step\'s walks and the '
+                         'loss terms (dump_outputs; the same arguments give the same inputs)')
     ap.add_argument('--batch-walks', type=int, default=None)
     ap.add_argument('--config', default='c3', choices=sorted(CONFIGS),
                     help='BASELINE workload preset: c2 = Cora-shaped R-MAT 12, node2vec, 64-walk '
@@ -664,7 +709,7 @@ def main():
                     help='after the timed steps, check one more step on a sample of rows against '
                          'a float64 restatement of the reference step from the full tables '
                          '(word2vec/verify.py; every rank gathers them); exit non-zero on a miss. '
-                         'auto = on for the owner layout with collectives (the N > 1 lines)')
+                         'auto = on for the --full N > 1 lines')
     ap.add_argument('--walk-prefetch', action='store_true',
                     help='generate the next batch\'s walks on a side stream during this step\'s '
                          'SGNS (measured neutral on MI355X: the SGNS slows by what the walker '
@@ -688,6 +733,11 @@ def main():
                          'fixed-point gradient sums, bit-identical tables run to run and across '
                          'ranks); dense in-table Adam and the records path, as that mode needs')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if not args.full:   # a plain run: the headline steps only
+        args.no_cpu_baseline = args.no_walk_bench = True
+        args.exact_steps = args.batch64_steps = args.c5_steps = 0
     if args.deterministic:
         # one GPU, sparse batches keep the lazy owner path (its rows-major step has the integer
         # sums); otherwise the dense in-table Adam and the records path
@@ -759,7 +809,8 @@ def run(args, world: int, rank: int, local_rank: int, backend: str, dist_on: boo
                                                     replicated_step)
     _native.require_device(dev)
 
-    copy_gbs = measured_copy_gbs(dev)   # before the tables take the memory
+    # (--full) before the tables take the memory
+    copy_gbs = measured_copy_gbs(dev) if args.full else None
     t0 = time.time()
     csr = rmat_graph(args.scale, args.edges, 0, device=dev)   # built in HBM (dw_rmat_edges)
     V = csr.vocab_size
@@ -1174,6 +1225,14 @@ def run(args, world: int, rank: int, local_rank: int, backend: str, dist_on: boo
     kern_ms = {k: float(np.mean([a.elapsed_time(b) for a, b in v])) for k, v in ev.items() if v}
     if graphed is not None:   # one replay = `unroll` steps
         kern_ms = {k: v / graphed.unroll for k, v in kern_ms.items()}
+    if args.dump_outputs and rank == 0:
+        if graphed is not None:
+            last_walks = graphed.walks[-B:]
+        elif owner and args.owner_walks == 'gather' and not emulate:
+            last_walks = walks_buf
+        else:
+            last_walks = feed.walks[(step_idx[0] - 1) % len(feed.walks)][:feed.n]
+        dump_outputs(args.dump_outputs, tables, owner, last_walks, loss_acc)
 
     # ---- the same step with the bit-exact walker ----------------------------
     # rng='python': the walks the reference's DeepWalk.walk / Node2Vec.walk take from CPython's
@@ -1228,7 +1287,7 @@ def run(args, world: int, rank: int, local_rank: int, backend: str, dist_on: boo
     # perturbs one sampled out row in the last rank's shard after the step: the check must fail.
     step_check = None
     want_check = (args.verify_step == 'on' or
-                  (args.verify_step == 'auto' and dist_on))
+                  (args.verify_step == 'auto' and dist_on and args.full))
     if want_check and (owner or dist_on) and not emulate and graphed is None and \
             (not owner or args.owner_walks == 'gather') and V * d * 4 * 6 <= (16 << 30):
         from shallow_encoders.word2vec import verify
@@ -1572,7 +1631,8 @@ def run(args, world: int, rank: int, local_rank: int, backend: str, dist_on: boo
                        if args.scatter == 'sorted' else 'dw_sgns_walks (k_sgns, atomic scatter)'),
             'bound': 'hbm', 'achieved': sgns_gbs, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
             'frac': sgns_gbs / HBM_PEAK_GBS, 'traffic': None,
-            'measured_copy_GBps': copy_gbs, 'frac_of_measured': sgns_gbs / copy_gbs,
+            'measured_copy_GBps': copy_gbs,
+            'frac_of_measured': sgns_gbs / copy_gbs if copy_gbs else None,
             'bytes_per_pair': bpp, 'pairs_per_launch': pairs_per_step,
             'out_table_adam_bytes': out_adam_bytes, 'in_table_adam_bytes': in_adam_bytes,
             'in_table_adam_blocks': (overlap_adam_blocks(V * d * 4 * 7, p2_bytes)

@@ -18,4 +18,4 @@ run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit 1
 run gpu_tests 1200 python -m pytest tests -m gpu -q -p no:cacheprovider -rf --timeout 600
 rc=$?
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo "stopping: pytest rc=$rc"; exit $rc; fi
-run bench 900 python bench.py ${BENCH_ARGS:-} || exit 1
+run bench 900 python bench.py --full ${BENCH_ARGS:-} || exit 1

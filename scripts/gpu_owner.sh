@@ -24,5 +24,5 @@ for W in ${EMU_WORLDS:-2 4 8}; do
 done
 step owner_rehearsal 300 env DW_BENCH_BACKEND=gloo DW_BENCH_ONE_DEVICE=1 \
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-  --master-port 29517 bench.py --gpus 2 --steps 4 --warmup 1 --no-cpu-baseline \
+  --master-port 29517 bench.py --full --gpus 2 --steps 4 --warmup 1 --no-cpu-baseline \
   --no-walk-bench || exit 1

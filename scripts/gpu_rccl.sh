@@ -19,10 +19,10 @@ run() {  # run <name> <timeout_s> <cmd...>
 TR="python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1"
 run rccl_test 400 python -u -m pytest tests/test_gpu_rccl.py -x -v --timeout 300 \
     --timeout-method thread -p no:cacheprovider || exit 1
-run rccl_c3_auto 300 $TR --master-port 29611 bench.py --steps 20 --warmup 3 --no-walk-bench || exit 1
-run rccl_c3_replicated 300 $TR --master-port 29612 bench.py --steps 20 --warmup 3 --no-walk-bench \
+run rccl_c3_auto 300 $TR --master-port 29611 bench.py --full --steps 20 --warmup 3 --no-walk-bench || exit 1
+run rccl_c3_replicated 300 $TR --master-port 29612 bench.py --full --steps 20 --warmup 3 --no-walk-bench \
     --dist-mode replicated || exit 1
-run rccl_c3_strong 300 $TR --master-port 29613 bench.py --steps 20 --warmup 3 --no-walk-bench \
+run rccl_c3_strong 300 $TR --master-port 29613 bench.py --full --steps 20 --warmup 3 --no-walk-bench \
     --scaling strong --in-exchange lazy || exit 1
-run rccl_c2 300 $TR --master-port 29614 bench.py --config c2 --steps 40 --warmup 3 --no-walk-bench || exit 1
-run rccl_c5 400 $TR --master-port 29615 bench.py --config c5 --steps 5 --warmup 2 --no-walk-bench || exit 1
+run rccl_c2 300 $TR --master-port 29614 bench.py --full --config c2 --steps 40 --warmup 3 --no-walk-bench || exit 1
+run rccl_c5 400 $TR --master-port 29615 bench.py --full --config c5 --steps 5 --warmup 2 --no-walk-bench || exit 1

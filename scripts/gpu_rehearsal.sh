@@ -12,7 +12,7 @@ step() {  # step <name> <nproc> <bench args...>
   echo "=== $name ($(date +%T))"
   timeout -k 10 300 env DW_BENCH_BACKEND=gloo DW_BENCH_ONE_DEVICE=1 \
     python -m torch.distributed.run --nnodes=1 --nproc-per-node "$np" --master-addr 127.0.0.1 \
-    --master-port $port bench.py --gpus "$np" --steps 4 --warmup 1 --no-cpu-baseline \
+    --master-port $port bench.py --full --gpus "$np" --steps 4 --warmup 1 --no-cpu-baseline \
     --no-walk-bench "$@" > "gpurun_out/$name.log" 2>&1
   local rc=$?
   echo "=== $name rc=$rc"

@@ -1,3 +1,4 @@
+import glob
 import os
 import sys
 
@@ -17,8 +18,26 @@ def pytest_configure(config):
     config.addinivalue_line('markers', 'slow: long-running parity case')
 
 
+class _GoldenParts(dict):
+    """A fixture stored as several .npz files (make_golden.save(parts=...): every committed file
+    stays under 1 MiB), read as one."""
+
+    @property
+    def files(self):
+        return list(self)
+
+
 def golden(name):
-    return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
+    path = os.path.join(GOLDEN, name)
+    f = np.load(path, allow_pickle=False)
+    parts = sorted(glob.glob(glob.escape(os.path.splitext(path)[0]) + '.part*.npz'))
+    if not parts:
+        return f
+    merged = _GoldenParts((k, f[k]) for k in f.files)
+    for p in parts:
+        with np.load(p, allow_pickle=False) as g:
+            merged.update((k, g[k]) for k in g.files)
+    return merged
 
 
 @pytest.fixture(scope='session')

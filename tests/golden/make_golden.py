@@ -99,10 +99,17 @@ class Capture:
         return False
 
 
-def save(name, **arrays):
+def save(name, parts=(), **arrays):
+    """``parts``: arrays written to files of their own (<stem>.part<i>.npz, read back with the
+    main file by conftest.golden), so that no committed file exceeds 1 MiB."""
     path = os.path.join(HERE, name)
-    np.savez_compressed(path, **arrays)
-    print(f'wrote {path} ({os.path.getsize(path)} bytes)')
+    files = [(path, {k: v for k, v in arrays.items() if k not in parts})]
+    files += [(f'{os.path.splitext(path)[0]}.part{i}.npz', {k: arrays[k]})
+              for i, k in enumerate(parts, 1)]
+    for p, group in files:
+        np.savez_compressed(p, **group)
+        assert os.path.getsize(p) <= 1 << 20, f'{p} is larger than 1 MiB: split it further'
+        print(f'wrote {p} ({os.path.getsize(p)} bytes)')
 
 
 # ------------------------------------------------------------------------------- walks
@@ -430,7 +437,8 @@ def trajectory128_fixture(name='traj_d128_k5_r5.npz', V=1025, d=128, R=5, K=5, l
         noises.append(noise)
         losses.append([float(loss['loss']), float(loss['positive-loss']),
                        float(loss['negative-loss'])])
-    save(name, V=V, d=d, R=R, K=K, lr=lr, init_seed=init_seed, noise_seed=noise_seed,
+    save(name, parts=('w_in0', 'w_out0', 'w_in', 'w_out'),
+         V=V, d=d, R=R, K=K, lr=lr, init_seed=init_seed, noise_seed=noise_seed,
          walks=walks.astype(np.int16), noise=np.stack(noises).astype(np.int16), w_in0=w_in0,
          w_out0=w_out0, w_in=model._input_embedding.weight.detach().numpy(),
          w_out=model._output_embedding.weight.detach().numpy(), losses=np.array(losses))
