@@ -311,7 +311,15 @@ __device__ __forceinline__ void adam_elem_g0_box2(f32x2 &p, f32x2 &m, f32x2 &v,
 // subnormal m_j is below 2^-126 / eps), so |y_j| <= F |m_k| / max(x_k, eps) (1 + 2^-24)^3, and
 // p is frozen once that is below |p| 2^-26 (< half the spacing below |p|) — tested with margins
 // in fp32 (frozen_el). m = +-0 freezes p too (y is a signed zero), except p = -0 with m = -0.
-// The same bits as the full steps (tests/test_gpu_owner.py::test_rows_adam_long_lag_bit_exact).
+// An F that is not a positive number (0, negative, NaN — a hand-built header with the tag, the
+// box step and zeros behind them reads as F = 0, betas 0) means the header certifies nothing and
+// no element is frozen, m = +-0 included (hist_freeze hands frozen_el a NaN): F = 0 would
+// certify every p != 0 as frozen, m = +-0 freezes under any F, and either tail would then run
+// v = v * 0 with the betas of [4], [5]. hist_betas is not consulted for such a header. (A history
+// whose every lr is 0 gets F = 0 from the host and just stops freezing: slower, the same bits.)
+// The same bits as the full steps (tests/test_gpu_owner.py::test_rows_adam_long_lag_bit_exact)
+// and as the IEEE restatement oracle/adam_ref.py under every header form
+// (tests/test_gpu_adam_ieee.py::test_rows_adam_long_lag_equals_oracle).
 struct Freeze {
     float F, eps;
 };
@@ -320,7 +328,10 @@ __device__ __forceinline__ Freeze hist_freeze(const float *__restrict__ hist) {
     typedef __attribute__((address_space(4))) const uint32_t const_u32;
     const const_u32 *h0 = (const const_u32 *)hist;
     if (h0[0] != DW_HIST_BOX_TAG) return Freeze{__builtin_huge_valf(), 0.f};
-    return Freeze{__uint_as_float(h0[2]), __uint_as_float(h0[3])};
+    const float F = __uint_as_float(h0[2]);
+    // 0, negative, NaN: not a certified header, nothing freezes (frozen_el: NaN, m = +-0 included)
+    if (!(F > 0.f)) return Freeze{__builtin_nanf(""), 0.f};
+    return Freeze{F, __uint_as_float(h0[3])};
 }
 
 // The history's constant betas (row 0 [4] = 1 - beta1, [5] = beta2, from sharding.hist_header:
@@ -340,7 +351,8 @@ __device__ __forceinline__ Betas hist_betas(const float *__restrict__ hist) {
 __device__ __forceinline__ bool frozen_el(float p, float m, float x, const Freeze &fz) {
 #pragma clang fp contract(off)
     const uint32_t mb = __float_as_uint(m), pb = __float_as_uint(p);
-    if ((mb & 0x7FFFFFFFu) == 0u) return !(pb == 0x80000000u && mb == 0x80000000u);
+    if ((mb & 0x7FFFFFFFu) == 0u)   // (F NaN: the header is not trusted, its betas neither)
+        return fz.F == fz.F && !(pb == 0x80000000u && mb == 0x80000000u);
     const float ap = fabsf(p);
     const float rhs = ap * fmaxf(x, fz.eps) * 0x1p-26f;
     return fz.F * fabsf(m) * (1.0f + 0x1p-18f) < rhs && rhs >= 0x1p-100f &&
@@ -423,9 +435,13 @@ __device__ __forceinline__ void replay_g0(float (&p)[N], float (&m)[N], float (&
                 const Betas hb = hist_betas(hist);
                 if (hb.ok) {
                     // constant betas: no per-step history loads (a steady-state catch-up replays
-                    // thousands of frozen steps a row), 8 steps a trip; once m is +0 in every
-                    // lane it stays +0 (fma(w1, -0, +0) = +0; a -0 becomes +0 in one step, so
-                    // only +0 ends the m updates) and v steps alone
+                    // thousands of frozen steps a row), 8 steps a trip; a wave whose m is +0 in
+                    // every lane keeps it (fma(w1, -0, +0) = +0; a -0 becomes +0 in one step, so
+                    // only +0 ends the m updates) and steps v alone. The kernels keep fp32
+                    // denormals, so m does not decay to +0 by itself: with w1 = 0.1f it sticks
+                    // at 4 units of 2^-149 (5 -> 4 -> 4), and only rows whose m started +-0 —
+                    // or w1 >= 0.5, where the last unit's half ties to even — get here
+                    // (oracle/adam_ref.py, tests/test_oracle_adam.py)
                     const f32x2 w1 = {hb.w1, hb.w1}, b2 = {hb.b2, hb.b2};
                     bool mzero = false;
                     while (s <= upto) {

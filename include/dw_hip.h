@@ -751,7 +751,9 @@ int dw_adam_dense_to(const float *param_src, float *param_dst, float *grad, floa
  *         fewer operations); [2] = F, [3] = eps of those rows: with every box row's eps equal to
  *         it, (1 - beta1)(1 + 2^-20) <= sqrt(beta2) and |nstep| <= F, a replay whose parameter
  *         can provably no longer move (|m| F / max(RN(sqrt(v)), eps) below |p| 2^-26) steps m
- *         and v alone for the rest of the run (the same bits; F = +inf: never); [4] = 1-beta1,
+ *         and v alone for the rest of the run (the same bits; F = +inf, or any F that is not a
+ *         positive number — 0, negative, NaN, so also zeros left behind [0] and [1]: never; under
+ *         the latter [3]..[5] are not read at all); [4] = 1-beta1,
  *         [5] = beta2 when every box row has those same values (the frozen steps then take them
  *         from here, not from each row; NaN = the betas vary); any other row 0 = no step in the
  *         box;

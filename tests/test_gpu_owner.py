@@ -310,9 +310,13 @@ def test_rows_adam_long_lag_bit_exact(hip_device, d, sched, S):
     moves runs m and v alone (dw::frozen_el) — the same bits as one dense dw_adam_dense per
     step, and as the same replay with the freeze disabled (header F = +inf). Rows include
     p = -0 with m = -0 (never frozen), m = 0 and p = 0; sched: the lr changes along the run.
-    With the betas constant the frozen steps take them from the header (no per-step loads) and,
-    once m is +0 in every lane (S = 2500: m underflows after ~900 steps), step v alone; the
-    header's betas withheld (NaN) gives the per-step form — the same bits again."""
+    With the betas constant the frozen steps take them from the header (no per-step loads); a
+    wave whose m is +0 in every lane (here only the row that starts with m = 0) steps v alone.
+    The kernels keep fp32 denormals, so m does not underflow to +0 by decay: with
+    1 - beta1 = 0.1f it goes subnormal after ~900 steps and sticks at 4 units of 2^-149
+    (S = 2500 reaches that; tests/test_oracle_adam.py, and tests/test_gpu_adam_ieee.py for the
+    device against the IEEE oracle). The header's betas withheld (NaN) gives the per-step form —
+    the same bits again."""
     import time
     from shallow_encoders.word2vec.sharding import hip_adam, hip_rows_adam, hist_header, hist_row
     g = torch.Generator().manual_seed(d)
