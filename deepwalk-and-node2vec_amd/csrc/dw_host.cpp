@@ -11,7 +11,9 @@
 // The caller passes the generator state as random.getstate()[1] (624 words + index) and writes
 // the advanced state back with random.setstate, so the global stream continues exactly where
 // Python's own shuffle would have left it.
+#include <math.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "dw_common.h"
 
@@ -86,6 +88,75 @@ int dw_host_shuffle(uint32_t *mt_state, int64_t *perm, int64_t n) {
         perm[j] = t;
     }
     mt_state[MT_N] = g.idx;
+    return DW_OK;
+}
+
+// Vose alias table over the whole vocabulary for dw_sgns_noise_alias (float64, serial, one-time):
+// k_alias_build's stack discipline (dw_graph.hip) on one row of V entries — the small list grows
+// from the front of `stack`, the large list from its back, both pop from the top — with the
+// entry packed as {alias id << 32 | prob_thr}. An id of weight 0 has scaled weight 0, so
+// prob_thr = 0 (never kept) when it meets a large id; one that rounding leaves on the small
+// stack after the large stack ran out gets prob_thr = 0 and the heaviest id (the first of them)
+// as its alias instead of "always". Restated in tests/noise_ref.py (Python floats: the same
+// IEEE operations in the same order).
+int dw_noise_alias_build(const double *weights, int64_t V, uint64_t *table) {
+#pragma clang fp contract(off)
+    DW_REQUIRE(V >= 1 && V < (int64_t(1) << 31),
+               "dw_noise_alias_build: vocab_size must be in [1, 2^31)");
+    DW_REQUIRE(weights && table, "dw_noise_alias_build: null pointer");
+    double sum = 0.0;
+    int64_t heaviest = 0;
+    for (int64_t i = 0; i < V; ++i) {
+        const double w = weights[i];
+        DW_REQUIRE(w >= 0.0 && w <= 1.7976931348623157e308,
+                   "dw_noise_alias_build: weight %lld is negative or not finite", (long long)i);
+        sum += w;
+        if (w > weights[heaviest]) heaviest = i;
+    }
+    DW_REQUIRE(sum > 0.0 && sum <= 1.7976931348623157e308,
+               "dw_noise_alias_build: the weights must have a positive, finite sum");
+    double *scaled = static_cast<double *>(malloc(sizeof(double) * static_cast<size_t>(V)));
+    int32_t *stack = static_cast<int32_t *>(malloc(sizeof(int32_t) * static_cast<size_t>(V)));
+    if (!scaled || !stack) {
+        free(scaled);
+        free(stack);
+        dw::set_error("dw_noise_alias_build: out of host memory for %lld entries", (long long)V);
+        return DW_E_UNSUPPORTED;
+    }
+    const auto entry = [](uint32_t thr, int64_t alias) {
+        return (static_cast<uint64_t>(alias) << 32) | thr;
+    };
+    int64_t ns = 0, nl = 0;
+    for (int64_t i = 0; i < V; ++i) {
+        const double s = weights[i] * static_cast<double>(V) / sum;
+        scaled[i] = s;
+        if (s < 1.0)
+            stack[ns++] = static_cast<int32_t>(i);
+        else
+            stack[V - 1 - nl++] = static_cast<int32_t>(i);
+    }
+    while (ns > 0 && nl > 0) {
+        const int32_t l = stack[--ns];
+        const int32_t g = stack[V - 1 - --nl];
+        const double pl = scaled[l];
+        table[l] = entry(static_cast<uint32_t>(fmin(floor(pl * 4294967296.0), 4294967295.0)), g);
+        const double pg = (scaled[g] + pl) - 1.0;
+        scaled[g] = pg;
+        if (pg < 1.0)
+            stack[ns++] = g;
+        else
+            stack[V - 1 - nl++] = g;
+    }
+    while (nl > 0) {
+        const int32_t g = stack[V - 1 - --nl];
+        table[g] = entry(0xFFFFFFFFu, g);
+    }
+    while (ns > 0) {
+        const int32_t l = stack[--ns];
+        table[l] = weights[l] == 0.0 ? entry(0u, heaviest) : entry(0xFFFFFFFFu, l);
+    }
+    free(scaled);
+    free(stack);
     return DW_OK;
 }
 

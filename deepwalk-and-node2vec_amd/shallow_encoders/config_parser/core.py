@@ -11,7 +11,11 @@ MI355X additions (all optional, defaulted, so reference configs load as they are
   datamodule.backend      'hip' (device walks straight into the fused kernel) | 'collate'
                           (the reference's DataLoader + W2VCollateFunctional batches)
   datamodule.additional_parameters.rng / seed   walker sampling mode (random_walk_generator)
-  train.noise             'torch' (reference-exact CPU noise) | 'device' (Philox on device)
+  train.noise             'torch' (reference-exact CPU noise) | 'device' (Philox on device) |
+                          'unigram' (graph datasets: negatives in proportion to
+                          degree ** train.noise_power, the word2vec / node2vec law; a departure
+                          from the reference's uniform noise)
+  train.noise_power       the unigram law's exponent (0.75)
   train.seed              seed for torch / Philox
 ``_target_: torch.optim.Adam`` instantiates the HIP Adam (word2vec/optim.py, same math).
 """
@@ -77,6 +81,7 @@ class TrainConfig:
     devices: str
     noise: str = 'torch'
     seed: int = 0
+    noise_power: float = 0.75
 
     def instantiate_optimizer(self, params: Iterator[nn.Parameter]) -> Optimizer:
         return instantiate(self.optimizer, params=params)
@@ -256,11 +261,33 @@ class GlobalConfig:
         optimizer = self.train.instantiate_optimizer(model.parameters()) \
             if optimizer is None else optimizer
         scheduler = self.train.instantiate_scheduler(optimizer) if scheduler is None else scheduler
+        extra = {}
+        if self.train.noise == 'unigram':
+            extra = dict(noise_weights=unigram_weights(dataset),
+                         noise_power=self.train.noise_power)
         return Word2VecTrainer(model=model, optimizer=optimizer, scheduler=scheduler,
                                neg_samples=self.train.loss.negative_samples,
                                vocab_size=len(dataset.vocab), noise=self.train.noise,
                                seed=self.train.seed,
-                               context_radius=self.datamodule.context_radius)
+                               context_radius=self.datamodule.context_radius, **extra)
+
+
+def unigram_weights(dataset) -> torch.Tensor:
+    """train.noise='unigram': float64 [V] weights by vocabulary id for a graph dataset — the
+    CSR's degrees, or the weighted degrees (each row's weights summed in order) of a weighted
+    graph; row 0 (``<unk>``, no neighbours) gets 0 and is never drawn. A text dataset has no
+    such table here: build the trainer with its own ``noise_weights``."""
+    import numpy as np
+    csr = getattr(getattr(dataset, 'dataset', None), 'csr', None)
+    if csr is None:
+        raise ValueError('train.noise=unigram takes its weights from a graph dataset\'s degrees; '
+                         'for a text dataset construct Word2VecTrainer(noise="unigram", '
+                         'noise_weights=<count per vocabulary id>) yourself')
+    deg = np.diff(csr.row_ptr)
+    if csr.weights is None:
+        return torch.from_numpy(deg.astype(np.float64))
+    rows = np.repeat(np.arange(len(deg)), deg)
+    return torch.from_numpy(np.bincount(rows, weights=csr.weights, minlength=len(deg)))
 
 
 # ------------------------------------------------------------------------------- loading

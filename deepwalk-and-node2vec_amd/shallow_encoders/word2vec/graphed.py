@@ -347,7 +347,9 @@ class GraphedTrainerStep:
     then the bit-exact replay walker. The negatives are the device Philox stream
     (``noise='device'``) or the reference's own (``noise='torch'``): torch.randint on the CPU
     generator's stream, likewise generated in HBM (DeviceMT.randint) for all the graph's steps at
-    its head. The Python and torch generators get their states back on ``release_rng`` (fit calls
+    its head; or (``noise='unigram'``) the unigram^power law from the trainer's alias table, drawn
+    inside each captured step under that step's bound block, with the device stream's keys. The
+    Python and torch generators get their states back on ``release_rng`` (fit calls
     it after the replays), exactly where the eager steps would have left them. The step is
     the trainer's own: the fused records step (the out table's Adam in the gather, the in
     table's on the side stream) or, for batches of <= 65,536 records, the atomic output-table
@@ -373,7 +375,7 @@ class GraphedTrainerStep:
             return False
         mine = {id(p) for p in opt.param_groups[0]['params']}
         return (getattr(walker, '_rng', None) in ('philox', 'python')
-                and trainer._noise_mode in ('device', 'torch')
+                and trainer._noise_mode in ('device', 'torch', 'unigram')
                 and trainer.manual_grads and trainer.model.max_norm is None
                 and mine == {id(w_in), id(w_out)} and w_in.device.type == 'cuda'
                 and trainer._context_radius is not None)
@@ -474,6 +476,8 @@ class GraphedTrainerStep:
         # so a replay never reaches freed memory whatever batch shapes the eager steps meet
         reg = getattr(trainer, '_exact', None)
         self._exact_refs = reg.live() if reg is not None else []
+        # likewise the buffer the captured steps fill with their negatives (noise='unigram')
+        self._noise_ref = trainer._noise_bufs.get((self.centres, 2 * R))
         torch.cuda.synchronize(dev)
 
     def _step_blk(self, k: int) -> int:

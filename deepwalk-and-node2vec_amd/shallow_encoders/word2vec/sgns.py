@@ -216,6 +216,50 @@ def device_noise(n_centres: int, n_ctx: int, neg_samples: int, vocab_size: int, 
     return out
 
 
+def unigram_table_host(weights: torch.Tensor, power: float = 0.75) -> torch.Tensor:
+    """The uint64 [V] alias table of ``weights ** power`` (dw_noise_alias_build: native host
+    code, no device needed) as a CPU tensor; entry = alias id << 32 | prob_thr. The power is
+    taken here, in float64 on the host, so the build is reproducible from the same doubles
+    (tests/noise_ref.py). Negative or non-finite weights and an all-zero vector are refused
+    (DWError); an id of weight 0 is never drawn."""
+    w = torch.as_tensor(weights).detach().double().cpu().reshape(-1).pow(float(power)).contiguous()
+    table = torch.empty(w.numel(), dtype=torch.uint64)
+    _native.call('dw_noise_alias_build', w.data_ptr(), int(w.numel()), table.data_ptr())
+    return table
+
+
+def unigram_table(weights: torch.Tensor, power: float = 0.75, device=None) -> torch.Tensor:
+    """``unigram_table_host`` on the HIP device (``device``: default the weights' device when
+    that is one, else the current device): the table ``unigram_noise`` draws from."""
+    if device is None and isinstance(weights, torch.Tensor) and weights.device.type == 'cuda':
+        device = weights.device
+    dev = _native.require_device(device)
+    return unigram_table_host(weights, power).to(dev)
+
+
+def unigram_noise(n_centres: int, n_ctx: int, neg_samples: int, table: torch.Tensor, seed: int,
+                  noise_offset: int, device, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int64 [B, C, K] negatives from the alias ``table`` (unigram_table) with the Philox stream
+    of ``device_noise`` (dw_sgns_noise_alias): equal weights give device_noise's ids. Under a
+    bound dw_step_scalars block the centre counter is the block's (graph replay). ``out``: a
+    contiguous int64 device tensor of B * C * K elements to fill instead of a new one."""
+    dev = table.device
+    want = torch.device(device) if device is not None else dev
+    if table.dtype != torch.uint64 or dev.type != 'cuda' or want.type != 'cuda' or \
+            (want.index is not None and want.index != dev.index):
+        raise ValueError('unigram_noise: table must be a uint64 tensor on the noise device')
+    n = int(n_centres) * int(n_ctx) * int(neg_samples)
+    if out is None:
+        out = torch.empty((n_centres, n_ctx, neg_samples), dtype=torch.int64, device=dev)
+    elif out.dtype != torch.int64 or out.numel() != n or out.device != dev:
+        raise ValueError('unigram_noise: out must be an int64 device tensor of B * C * K elements')
+    with torch.cuda.device(dev):
+        _native.call('dw_sgns_noise_alias', int(n_centres), int(n_ctx), int(neg_samples),
+                     int(table.numel()), _native.ptr(table), seed & 0xFFFFFFFFFFFFFFFF,
+                     int(noise_offset), _native.ptr(out), _native.stream(dev))
+    return out.view(n_centres, n_ctx, neg_samples)
+
+
 _RENORM_WS: Dict[torch.device, torch.Tensor] = {}
 
 

@@ -33,6 +33,10 @@ Same update as SGNS + ``optimizer.step()`` up to float-atomic summation order
 Noise: ``noise='torch'`` draws the reference's uniform negatives with torch's global CPU
 generator (generate_noise_batch, exact under ``torch.manual_seed``); ``noise='device'`` draws
 the same law on the device (Philox keyed by ``seed`` and the running centre counter).
+``noise='unigram'`` (a documented departure from the reference's uniform law: what word2vec.c,
+gensim and the node2vec reference code draw) draws negatives in proportion to
+``noise_weights ** noise_power`` (0.75) on the device, from an alias table over the vocabulary
+built once (sgns.unigram_table), with the same Philox keys; an id of weight 0 is never drawn.
 
 Deviation (documented): per-step loss values stay on the device; the reference's per-step
 ``.detach().cpu()`` NaN assert (trainer.py:116,121) runs once per epoch instead.
@@ -46,7 +50,8 @@ from shallow_encoders import _native
 from shallow_encoders.word2vec import exact
 from shallow_encoders.word2vec.model import W2VBase
 from shallow_encoders.word2vec.sgns import (SGNSLoss, _use_records, device_noise, loss_terms,
-                                            renorm_, sgns_accumulate, sgns_phase_bytes)
+                                            renorm_, sgns_accumulate, sgns_phase_bytes,
+                                            unigram_noise, unigram_table_host)
 from shallow_encoders.word2vec.utils import torch_helper
 from shallow_encoders.word2vec.utils.meter import MetricMeter
 from shallow_encoders.word2vec.utils.sampling import generate_noise_batch
@@ -64,10 +69,26 @@ class Word2VecTrainer(_Base):
     """Trains a W2V model with the fused SGNS kernel."""
 
     def __init__(self, model: W2VBase, optimizer: Optimizer, scheduler, neg_samples: int,
-                 vocab_size: int, noise: str = 'torch', seed: int = 0, context_radius: int = None):
+                 vocab_size: int, noise: str = 'torch', seed: int = 0, context_radius: int = None,
+                 noise_weights: torch.Tensor = None, noise_power: float = 0.75):
         super().__init__()
-        if noise not in ('torch', 'device'):
-            raise ValueError('noise must be "torch" or "device"')
+        if noise not in ('torch', 'device', 'unigram'):
+            raise ValueError('noise must be "torch", "device" or "unigram"')
+        # noise='unigram': the alias table over the vocabulary, built here on the host (native
+        # code, no device needed) and moved to the tables' device by the first step
+        self._noise_table_host = self._noise_table = None
+        self._noise_bufs: Dict[tuple, torch.Tensor] = {}
+        if noise == 'unigram':
+            if noise_weights is None:
+                raise ValueError('noise="unigram" needs noise_weights: one non-negative weight '
+                                 'per vocabulary id (counts or degrees; id 0 is <unk>)')
+            noise_weights = torch.as_tensor(noise_weights)
+            if noise_weights.dim() != 1 or noise_weights.numel() != vocab_size:
+                raise ValueError(f'noise_weights must have vocab_size = {vocab_size} entries, got '
+                                 f'shape {tuple(noise_weights.shape)}')
+            self._noise_table_host = unigram_table_host(noise_weights, noise_power)
+        elif noise_weights is not None:
+            raise ValueError('noise_weights is only used by noise="unigram"')
         self._optimizer = optimizer
         self._scheduler = scheduler
         self._neg_samples = neg_samples
@@ -151,8 +172,30 @@ class Word2VecTrainer(_Base):
             return None
         if self._noise_override is not None:
             return self._noise_override
+        if self._noise_mode == 'unigram':
+            return self._unigram_noise(n_centres, n_ctx, torch.device(device))
         noise = generate_noise_batch(n_centres, n_ctx, self._neg_samples, self._vocab_size)
         return noise.to(device, non_blocking=True)
+
+    # at most this many step shapes keep their negatives' buffer (text batches vary in size)
+    NOISE_BUFFERS = 8
+
+    def _unigram_noise(self, n_centres: int, n_ctx: int, dev: torch.device) -> torch.Tensor:
+        """This step's negatives (the centre counter is not yet advanced) in the persistent
+        buffer of its shape: a captured step allocates nothing, and its replays fill the buffer
+        they were captured with (GraphedTrainerStep holds on to it)."""
+        if self._noise_table is None or self._noise_table.device != dev:
+            self._noise_table = self._noise_table_host.to(dev)
+            self._noise_bufs.clear()
+        key = (n_centres, n_ctx)
+        buf = self._noise_bufs.pop(key, None)
+        if buf is None:
+            buf = torch.empty((n_centres, n_ctx, self._neg_samples), dtype=torch.int64, device=dev)
+            while len(self._noise_bufs) >= self.NOISE_BUFFERS:   # the least recently used
+                self._noise_bufs.pop(next(iter(self._noise_bufs)))
+        self._noise_bufs[key] = buf
+        return unigram_noise(n_centres, n_ctx, self._neg_samples, self._noise_table, self._seed,
+                             self._noise_offset, dev, out=buf)
 
     def training_step(self, batch, *args, **kwargs) -> Dict[str, torch.Tensor]:
         w_in = self._model.input_weight

@@ -653,6 +653,33 @@ int dw_sgns_pooled_pairs(const int64_t *inputs, int32_t n_in, const int64_t *tar
 int dw_sgns_noise(int64_t batch, int32_t n_ctx, int32_t neg_samples, int64_t vocab_size,
                   uint64_t seed, uint64_t noise_offset, int64_t *noise, void *stream);
 
+/* ---- unigram^power negatives (noise='unigram') ---------------------------------------------
+ * A documented DEPARTURE from the reference's law: generate_noise_batch (utils/sampling.py:7-21)
+ * draws negatives uniformly over [0, V); word2vec.c, gensim and the node2vec reference code draw
+ * them from the unigram law raised to 0.75. These two entry points draw from any weight vector
+ * over the vocabulary (the caller raises its counts or degrees to the power itself).
+ *
+ * dw_noise_alias_build (HOST, no device work; weights and table are HOST buffers): the Vose
+ * alias table of weights[0..V) in float64 — scaled weight w[i] * V / sum, the small list
+ * growing from the front of one stack, the large list from its back, both popping from the top
+ * (dw_alias_build's discipline). table[i] = {alias id << 32 | prob_thr}, prob_thr =
+ * floor(p * 2^32) with 0xFFFFFFFF = always keep i. An id of weight 0 is never drawn: its
+ * prob_thr is 0, also where rounding leaves it on the small stack after the large stack ran out
+ * (its alias is then the first id of the largest weight). DW_E_INVALID_ARG for V < 1,
+ * V >= 2^31, a negative or non-finite weight, or a sum that is not positive and finite.
+ *
+ * dw_sgns_noise_alias (table: DEVICE uint64[vocab_size]): noise[(b*n_ctx + j)*K + k] for
+ * b < batch from the Philox call of dw_sgns_noise — counter (g lo, g hi, n >> 1, 'SG') with
+ * g = noise_offset + b, n = j*K + k, words (x, y) = (lo, hi) for even n and (z, w) for odd n.
+ * With T = hi*V + ((lo*V) >> 32): slot i = T >> 32 (dw_sgns_noise's id), f = T's low word
+ * (the fraction of r64 * V / 2^64), id = i when prob_thr(i) is 0xFFFFFFFF or f < prob_thr(i),
+ * else alias(i). Equal weights give dw_sgns_noise's output bit for bit. With a dw_step_scalars
+ * block bound, noise_offset is read from it (a captured step draws each replay's negatives). */
+int dw_noise_alias_build(const double *weights, int64_t V, uint64_t *table);
+int dw_sgns_noise_alias(int64_t batch, int32_t n_ctx, int32_t neg_samples, int64_t vocab_size,
+                        const uint64_t *table, uint64_t seed, uint64_t noise_offset,
+                        int64_t *noise, void *stream);
+
 /* nn.Embedding(max_norm=...) lookup side effect (model.py:24-25 with max_norm set; torch
  * embedding_renorm_): every DISTINCT row among ids[0..n_ids) whose L2 norm exceeds max_norm is
  * scaled by max_norm / (norm + 1e-7), in place. Ids are deduplicated on the device (radix sort
@@ -787,7 +814,7 @@ int dw_scale(float *x, int64_t n_elem, float alpha, const float *alpha_dev, void
  * step to step live in device memory instead of kernel arguments: while a dw_step_scalars block
  * is BOUND (dw_step_scalars_bind, per host thread), every launch of
  *   dw_walk_fast / dw_walk_fast_indexed / dw_walk_fast_positions   reads walk_id0 from it,
- *   dw_sgns_walks_phase (pass 1)          reads noise_offset from it,
+ *   dw_sgns_walks_phase (pass 1), dw_sgns_noise_alias   read noise_offset from it,
  *   dw_adam_dense(_to), dw_sgns_walks_phase2_adam   read the Adam scalars adam[0..6],
  * and ignores the corresponding host arguments. dw_step_scalars_advance, the last node of a
  * captured step, moves the block to the next step. Nothing else changes: the kernels and their
