@@ -116,6 +116,33 @@ __device__ __forceinline__ double wave_sum_d(double x) {
     return x;
 }
 
+// Loss terms and gradient coefficient of one output row (loss.py:14-22 + its autograd):
+//   positive row: -log(clamp(sigmoid(x), 1e-6)),  d/dx = sigmoid(x) - 1  where unclamped;
+//   negative row: -log(clamp(sigmoid(-x), 1e-6)), d/dx = 1 - sigmoid(-x) where unclamped;
+// recall counts positives with sigmoid(x) >= 0.5, the precision tally negatives with it.
+// One exp(-|x|) and one reciprocal give sigmoid(|x|) and sigmoid(-|x|) together (finite for
+// every x); the hardware exp / rcp / log (a few ulp) keep the per-row dependency chain short —
+// this chain, not memory, bounded pass 1 with the libm versions. The (s - 1) / (1 - s) forms
+// keep the reference's rounding structure.
+__device__ __forceinline__ float row_coef(float x, bool pos, float scale, float &acc_pos,
+                                          float &acc_neg, float &acc_rec, float &acc_prec) {
+    const float e = __expf(-fabsf(x));
+    const float hi = __builtin_amdgcn_rcpf(1.0f + e);  // sigmoid(|x|)
+    const float lo = e * hi;                            // sigmoid(-|x|)
+    const float sp = x >= 0.f ? hi : lo;                // sigmoid(x)
+    const float sy = pos ? sp : (x >= 0.f ? lo : hi);   // sigmoid(x) / sigmoid(-x)
+    const float loss = -__logf(fmaxf(sy, 1e-6f));
+    const float hit = sp >= 0.5f ? 1.f : 0.f;
+    if (pos) {
+        acc_pos += loss;
+        acc_rec += hit;
+    } else {
+        acc_neg += loss;
+        acc_prec += hit;
+    }
+    return sy >= 1e-6f ? (pos ? sy - 1.0f : 1.0f - sy) * scale : 0.f;
+}
+
 // torch.optim.Adam single-tensor update of one element (dw_adam.hip; also fused into the SGNS
 // output-table pass). Scalars precomputed on the host in float64, cast to float32.
 struct AdamScalars {

@@ -38,7 +38,7 @@ DW_EXACT_ADAM = 2
 DW_METHOD_DEEPWALK = 0
 DW_METHOD_NODE2VEC = 1
 
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 _p = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -120,6 +120,8 @@ SIGNATURES = {
     'dw_sgns_walks_phase2_adam': (ctypes.c_int, [_p, _i64, _i32, _i32, _i32, _i64, _i32, _p, _p,
                                                  _p, _p, _p, _p, _f32, _f32, _f32, _f32, _f32,
                                                  _f32, _f32, _p, _p, ctypes.c_size_t, _p]),
+    'dw_sgns_walks_shared': (ctypes.c_int, [_p, _i64, _i32, _i32, _i32, _i32, _i64, _i32, _p, _p,
+                                            _p, _p, _p, _f32, _p, _p, _p]),
     'dw_sgns_pairs': (ctypes.c_int, [_p, _p, _i64, _i32, _i32, _i64, _i32, _p, _p, _p, _p,
                                      _p, _u64, _u64, _f32, _p, _p, _p, ctypes.c_size_t, _p]),
     'dw_sgns_workspace_bytes': (ctypes.c_int, [_i64, _i32, _i32, _i64, _szp]),

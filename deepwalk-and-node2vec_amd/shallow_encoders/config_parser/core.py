@@ -17,6 +17,10 @@ MI355X additions (all optional, defaulted, so reference configs load as they are
                           from the reference's uniform noise)
   train.noise_power       the unigram law's exponent (0.75)
   train.seed              seed for torch / Philox
+  train.shared_negatives  0 (off) | S in {32, 64, 96, 128}: the centres of a walk share S negatives
+                          drawn once per walk (noise 'device' or 'unigram'), the step one MFMA
+                          kernel (dw_sgns_walks_shared) and the optimizer's dense Adam; a departure
+                          from the reference's negatives per pair
 ``_target_: torch.optim.Adam`` instantiates the HIP Adam (word2vec/optim.py, same math).
 """
 import copy
@@ -82,6 +86,7 @@ class TrainConfig:
     noise: str = 'torch'
     seed: int = 0
     noise_power: float = 0.75
+    shared_negatives: int = 0
 
     def instantiate_optimizer(self, params: Iterator[nn.Parameter]) -> Optimizer:
         return instantiate(self.optimizer, params=params)
@@ -269,7 +274,8 @@ class GlobalConfig:
                                neg_samples=self.train.loss.negative_samples,
                                vocab_size=len(dataset.vocab), noise=self.train.noise,
                                seed=self.train.seed,
-                               context_radius=self.datamodule.context_radius, **extra)
+                               context_radius=self.datamodule.context_radius,
+                               shared_negatives=self.train.shared_negatives, **extra)
 
 
 def unigram_weights(dataset) -> torch.Tensor:

@@ -341,7 +341,7 @@ class GraphedTrainerStep:
     64-walk batches are launch-bound when stepped from Python one kernel at a time.
 
     Eligible (``eligible``): a RandomWalkDataset, ``manual_grads``, the HIP Adam holding exactly
-    the two tables, no ``max_norm``. The walks are the Philox walker's, or (``rng='python'``) the
+    the two tables, no ``max_norm``, no ``shared_negatives`` (that step is not captured yet). The walks are the Philox walker's, or (``rng='python'``) the
     reference's own: the walker's CPython random.random() stream generated in HBM by a generator
     whose state stays there across replays (graph/rng.py DeviceMT, the index read on the device),
     then the bit-exact replay walker. The negatives are the device Philox stream
@@ -377,6 +377,7 @@ class GraphedTrainerStep:
         return (getattr(walker, '_rng', None) in ('philox', 'python')
                 and trainer._noise_mode in ('device', 'torch', 'unigram')
                 and trainer.manual_grads and trainer.model.max_norm is None
+                and not getattr(trainer, '_shared', 0)
                 and mine == {id(w_in), id(w_out)} and w_in.device.type == 'cuda'
                 and trainer._context_radius is not None)
 

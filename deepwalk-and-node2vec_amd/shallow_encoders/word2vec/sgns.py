@@ -205,15 +205,99 @@ def sgns_phase2_pieces(w_in: torch.Tensor, g_out: torch.Tensor, neg_samples: int
 
 
 def device_noise(n_centres: int, n_ctx: int, neg_samples: int, vocab_size: int, seed: int,
-                 noise_offset: int, device) -> torch.Tensor:
+                 noise_offset: int, device, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """int64 [B, C, K]: the negatives the fused kernels draw for ``noise=None`` (same Philox
-    keys), materialised — needed when rows must be renormalised before the step (max_norm)."""
-    out = torch.empty((n_centres, n_ctx, neg_samples), dtype=torch.int64, device=device)
+    keys), materialised — needed when rows must be renormalised before the step (max_norm) and
+    as the shared negatives' ids (B = n_walks, C = 1, K = S). ``out``: a contiguous int64 device
+    tensor of B * C * K elements to fill instead of a new one."""
+    n = int(n_centres) * int(n_ctx) * int(neg_samples)
+    if out is None:
+        out = torch.empty((n_centres, n_ctx, neg_samples), dtype=torch.int64, device=device)
+    elif out.dtype != torch.int64 or out.numel() != n or out.device.type != 'cuda':
+        raise ValueError('device_noise: out must be an int64 device tensor of B * C * K elements')
+    else:
+        device = out.device
+        out = out.view(n_centres, n_ctx, neg_samples)
     with torch.cuda.device(device):
         _native.call('dw_sgns_noise', int(n_centres), int(n_ctx), int(neg_samples),
                      int(vocab_size), seed & 0xFFFFFFFFFFFFFFFF, int(noise_offset),
                      _native.ptr(out), _native.stream(device))
     return out
+
+
+# dw_sgns_walks_shared's shapes (include/dw_hip.h)
+SHARED_DIMS = (64, 128, 256)
+SHARED_MAX_L = 128
+SHARED_MAX_S = 128
+
+
+def shared_shape_error(L: int, R: int, S: int, d: int, V: int) -> Optional[str]:
+    """Why dw_sgns_walks_shared refuses this shape, or None when it takes it."""
+    if R < 1 or L < 2 * R + 1:
+        return f'walk_length {L} < 2R+1 (R = {R})'
+    if L > SHARED_MAX_L:
+        return f'walk_length {L} > {SHARED_MAX_L}'
+    if d not in SHARED_DIMS:
+        return f'dim must be one of {SHARED_DIMS}, got {d}'
+    if S % 32 or not 32 <= S <= SHARED_MAX_S:
+        return f'shared_negatives must be a multiple of 32 in [32, {SHARED_MAX_S}], got {S}'
+    if V >= 2 ** 31:
+        return 'vocab_size must be < 2^31'
+    return None
+
+
+def sgns_shared_accumulate(w_in: torch.Tensor, w_out: torch.Tensor, g_in: torch.Tensor,
+                           g_out: torch.Tensor, neg_samples: int, *, walks: torch.Tensor,
+                           context_radius: int, shared_ids: torch.Tensor,
+                           grad_scale: Optional[float] = None,
+                           loss_acc: Optional[torch.Tensor] = None,
+                           status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Launch the shared-negatives SGNS kernel (dw_sgns_walks_shared); returns the float64[4]
+    loss accumulator.
+
+    ``walks``: int32 [n_walks, L]; ``shared_ids``: int64 with n_walks * S elements ([n_walks, S]
+    or device_noise / unigram_noise's [n_walks, 1, S]) — walk w's L - 2R centres all take ids
+    [w, :] as their negatives, each weighted 2R * neg_samples / S; the contexts are the walk's
+    own nodes as in ``sgns_accumulate(walks=...)``. Gradients of the batch-mean loss are added
+    into ``g_in`` / ``g_out`` (``grad_scale`` defaults to 1 / (B' * 2R)); the loss sums work
+    with ``loss_terms(acc, B' * 2R, neg_samples)`` unchanged. Shapes outside the kernel's limits
+    (shared_shape_error) raise DWError."""
+    dev = w_in.device
+    V, d = w_in.shape
+    if w_out.shape != (V, d) or g_in.shape != (V, d) or g_out.shape != (V, d):
+        raise ValueError('embedding tables and gradients must all be (V, d)')
+    for t in (w_in, w_out, g_in, g_out):
+        if t.dtype != torch.float32:
+            raise TypeError('embedding tables and gradients must be float32')
+    if walks.dtype != torch.int32 or walks.dim() != 2:
+        raise TypeError('walks must be int32 [n_walks, L]')
+    n, L = walks.shape
+    if shared_ids.dtype != torch.int64 or n == 0 or shared_ids.numel() % n:
+        raise ValueError('shared_ids must be int64 with n_walks * S entries')
+    S = shared_ids.numel() // n
+    R, K = int(context_radius), int(neg_samples)
+    scale = 1.0 / max(n * (L - 2 * R) * 2 * R, 1) if grad_scale is None else grad_scale
+    if loss_acc is None:
+        loss_acc = torch.zeros(4, dtype=torch.float64, device=dev)
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _native.call('dw_sgns_walks_shared', _native.ptr(walks), n, L, R, K, S, V, d,
+                     _native.ptr(w_in), _native.ptr(w_out), _native.ptr(g_in), _native.ptr(g_out),
+                     _native.ptr(shared_ids), float(scale), _native.ptr(loss_acc),
+                     _native.ptr(status), _native.stream(dev))
+    return loss_acc
+
+
+def sgns_shared_bytes(n_walks: int, L: int, R: int, S: int, d: int) -> Dict[str, float]:
+    """Byte model of dw_sgns_walks_shared per call. Per walk: L - 2R centre
+    rows and L + S out rows of 4d B are read once from HBM / L2 into LDS ('reads') and a second
+    time from L2 as the gradient products' operands ('l2_reads', not HBM traffic when a walk's
+    rows stay resident between the two); every one of those rows leaves as one float-atomic
+    row, counted read + write ('atomics'); plus the walk and its ids."""
+    rows = n_walks * ((L - 2 * R) + (L + S))
+    return {'reads': rows * 4 * d + n_walks * (4 * L + 8 * S), 'l2_reads': rows * 4 * d,
+            'atomics': rows * 8 * d, 'atomic_rows': rows * 4 * d}
 
 
 def unigram_table_host(weights: torch.Tensor, power: float = 0.75) -> torch.Tensor:

@@ -38,6 +38,15 @@ gensim and the node2vec reference code draw) draws negatives in proportion to
 ``noise_weights ** noise_power`` (0.75) on the device, from an alias table over the vocabulary
 built once (sgns.unigram_table), with the same Philox keys; an id of weight 0 is never drawn.
 
+Shared negatives (``shared_negatives=S`` > 0; off by default, a documented departure from the
+reference): the L - 2R centres of a walk share S negatives drawn once per
+walk under the chosen law ('device' or 'unigram'), each weighted 2R K / S so the loss keeps its
+expectation and scale. A device walk batch then runs one MFMA kernel (dw_sgns_walks_shared: no
+per-pair gathers, no records, no sort) into ``param.grad`` and the optimizer's ordinary dense
+``step()`` applies the update. Needs ``manual_grads``; refuses ``noise='torch'`` and
+``max_norm`` (constructor), the deterministic mode, pairs / CBOW batches and shapes outside the
+kernel's limits (first step). Graph replay does not cover it (GraphedTrainerStep.eligible).
+
 Deviation (documented): per-step loss values stay on the device; the reference's per-step
 ``.detach().cpu()`` NaN assert (trainer.py:116,121) runs once per epoch instead.
 """
@@ -51,6 +60,7 @@ from shallow_encoders.word2vec import exact
 from shallow_encoders.word2vec.model import W2VBase
 from shallow_encoders.word2vec.sgns import (SGNSLoss, _use_records, device_noise, loss_terms,
                                             renorm_, sgns_accumulate, sgns_phase_bytes,
+                                            sgns_shared_accumulate, shared_shape_error,
                                             unigram_noise, unigram_table_host)
 from shallow_encoders.word2vec.utils import torch_helper
 from shallow_encoders.word2vec.utils.meter import MetricMeter
@@ -70,10 +80,21 @@ class Word2VecTrainer(_Base):
 
     def __init__(self, model: W2VBase, optimizer: Optimizer, scheduler, neg_samples: int,
                  vocab_size: int, noise: str = 'torch', seed: int = 0, context_radius: int = None,
-                 noise_weights: torch.Tensor = None, noise_power: float = 0.75):
+                 noise_weights: torch.Tensor = None, noise_power: float = 0.75,
+                 shared_negatives: int = 0):
         super().__init__()
         if noise not in ('torch', 'device', 'unigram'):
             raise ValueError('noise must be "torch", "device" or "unigram"')
+        self._shared = int(shared_negatives)
+        if self._shared < 0:
+            raise ValueError('shared_negatives must be >= 0 (0: off)')
+        if self._shared > 0:
+            if noise == 'torch':
+                raise ValueError('shared_negatives draws one block of ids per walk: the '
+                                 'reference\'s noise="torch" stream (one draw per pair) has no '
+                                 'meaning there; use noise="device" or "unigram"')
+            if getattr(model, 'max_norm', None) is not None:
+                raise ValueError('shared_negatives does not support max_norm')
         # noise='unigram': the alias table over the vocabulary, built here on the host (native
         # code, no device needed) and moved to the tables' device by the first step
         self._noise_table_host = self._noise_table = None
@@ -197,10 +218,75 @@ class Word2VecTrainer(_Base):
         return unigram_noise(n_centres, n_ctx, self._neg_samples, self._noise_table, self._seed,
                              self._noise_offset, dev, out=buf)
 
+    def _shared_ids(self, n_walks: int, offset: int, dev: torch.device) -> torch.Tensor:
+        """int64 [n_walks, 1, S]: the step's shared negatives, walk w's from the Philox centre
+        counter ``offset + w`` under the trainer's noise law, in the persistent buffer of the
+        shape (as _unigram_noise keeps its buffers)."""
+        S = self._shared
+        if self._noise_mode == 'unigram' and (self._noise_table is None
+                                              or self._noise_table.device != dev):
+            self._noise_table = self._noise_table_host.to(dev)
+            self._noise_bufs.clear()
+        key = ('shared', n_walks, S)
+        buf = self._noise_bufs.pop(key, None)
+        if buf is None or buf.device != dev:
+            buf = torch.empty((n_walks, 1, S), dtype=torch.int64, device=dev)
+            while len(self._noise_bufs) >= self.NOISE_BUFFERS:   # the least recently used
+                self._noise_bufs.pop(next(iter(self._noise_bufs)))
+        self._noise_bufs[key] = buf
+        if self._noise_mode == 'unigram':
+            return unigram_noise(n_walks, 1, S, self._noise_table, self._seed, offset, dev,
+                                 out=buf)
+        return device_noise(n_walks, 1, S, self._vocab_size, self._seed, offset, dev, out=buf)
+
+    def _shared_step(self, batch, w_in, w_out) -> Dict[str, torch.Tensor]:
+        """The shared-negatives step (module docstring): ids for the batch's walks, then
+        dw_sgns_walks_shared into the two gradient buffers; the update is the optimizer's."""
+        from shallow_encoders.word2vec.optim import Adam
+        if not isinstance(batch, torch.Tensor):
+            raise ValueError('shared_negatives takes device walk batches [n_walks, L], not '
+                             '(inputs, targets) pairs / CBOW batches')
+        if exact.enabled():
+            raise ValueError('shared_negatives has no deterministic mode (float atomics)')
+        if not self.manual_grads:
+            raise ValueError('shared_negatives needs manual_grads = True (the kernel adds into '
+                             'param.grad; there is no autograd form)')
+        R = self._context_radius
+        if R is None:
+            raise ValueError('walk batches need context_radius (set it on the trainer)')
+        dev = w_in.device
+        walks = batch if batch.dtype == torch.int32 else batch.to(torch.int32)
+        walks = walks.to(dev).contiguous()
+        n, L = walks.shape
+        bad = shared_shape_error(L, R, self._shared, w_in.shape[1], w_in.shape[0])
+        if bad is not None:
+            raise ValueError(f'shared_negatives: {bad}')
+        n_centres, C = n * (L - 2 * R), 2 * R
+        offset = self._noise_offset
+        ids = self._shared_ids(n, offset, dev)
+        self._noise_offset += n_centres
+        fresh = [p for p in (w_in, w_out) if p.grad is None]
+        for p in fresh:
+            p.grad = torch.zeros_like(p)
+        acc = sgns_shared_accumulate(w_in.detach(), w_out.detach(), w_in.grad, w_out.grad,
+                                     self._neg_samples, walks=walks, context_radius=R,
+                                     shared_ids=ids)
+        if isinstance(self._optimizer, Adam):
+            self._optimizer.mark_grads([w_in, w_out], False)   # accumulated, not consumed
+        t = loss_terms(acc, n_centres * C, self._neg_samples)
+        loss = {k: t[k] for k in ('loss', 'positive-loss', 'negative-loss')}
+        self._log_loss(loss, prefix='train', log_step=True)
+        self.log('epoch/lr', torch_helper.get_optim_lr(self.optimizer))
+        self._meter.push('train-metrics/recall', t['recall'])
+        self._meter.push('train-metrics/precision', t['precision'])
+        return loss
+
     def training_step(self, batch, *args, **kwargs) -> Dict[str, torch.Tensor]:
         w_in = self._model.input_weight
         w_out = self._model.output_weight
         dev = w_in.device
+        if self._shared:
+            return self._shared_step(batch, w_in, w_out)
         if isinstance(batch, torch.Tensor):           # device walks [n, L]
             R = self._context_radius
             if R is None:

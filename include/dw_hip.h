@@ -647,6 +647,30 @@ int dw_sgns_pooled_pairs(const int64_t *inputs, int32_t n_in, const int64_t *tar
                          uint64_t noise_offset, float grad_scale, double *loss_acc,
                          int32_t *status, void *stream);
 
+/* Shared-negatives SGNS over walks (a documented DEPARTURE from the reference):
+ * the L - 2R centres of walk w share the n_shared = S ids shared_ids[w, 0..S) as their negatives
+ * instead of drawing 2R x K each; the contexts are the walk's own nodes as in dw_sgns_walks. With
+ * lambda = 2R * K / S (K = neg_samples stays the nominal negatives per pair, so the loss keeps
+ * its expectation and scale):
+ *   loss_acc[0] += sum_i sum_ctx -log max(sigmoid(h_i . o_ctx), 1e-6),  [2] += count(sigmoid >= .5)
+ *   loss_acc[1] += lambda * sum_i sum_s -log max(sigmoid(-h_i . o_s), 1e-6),
+ *   loss_acc[3] += lambda * count(sigmoid(h_i . o_s) >= .5)
+ * and g_in / g_out += the closed-form gradient of exactly that loss times grad_scale (positive
+ * coefficient (sigmoid - 1) * scale, negative (1 - sigmoid(-x)) * lambda * scale, 0 where the
+ * clamp cuts). An id that repeats among a walk's S ids or equals a walk node is its own term.
+ * Ids outside [0, V) set DW_S_BAD_INDEX and drop their terms (dw_sgns_walks's convention).
+ *   shared_ids: int64[n_walks, n_shared], e.g. dw_sgns_noise(batch = n_walks, n_ctx = 1,
+ *               neg_samples = S) or dw_sgns_noise_alias.
+ * One block per walk: logits and both gradients are 32x32 f32-MFMA products, every gradient row
+ * leaves as float atomics; no workspace. Supported: dim in {64, 128, 256}; n_shared a multiple of
+ * 32 in [32, 128]; 2R + 1 <= walk_length <= 128; vocab_size < 2^31; anything else is
+ * DW_E_INVALID_ARG (checked before any device call). */
+int dw_sgns_walks_shared(const int32_t *walks, int64_t n_walks, int32_t walk_length,
+                         int32_t context_radius, int32_t neg_samples, int32_t n_shared,
+                         int64_t vocab_size, int32_t dim, const float *w_in, const float *w_out,
+                         float *g_in, float *g_out, const int64_t *shared_ids, float grad_scale,
+                         double *loss_acc, int32_t *status, void *stream);
+
 /* The device negatives dw_sgns_* draw when noise == NULL, written out: noise[(b*n_ctx + j)*K + k]
  * for b < batch (centre counter noise_offset + b). Replaces generate_noise_batch
  * (utils/sampling.py:7-21) where the ids must exist before the step (max_norm renormalisation).*/
