@@ -38,7 +38,7 @@ DW_EXACT_ADAM = 2
 DW_METHOD_DEEPWALK = 0
 DW_METHOD_NODE2VEC = 1
 
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 _p = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -130,6 +130,11 @@ SIGNATURES = {
     'dw_sgns_noise': (ctypes.c_int, [_i64, _i32, _i32, _i64, _u64, _u64, _p, _p]),
     'dw_noise_alias_build': (ctypes.c_int, [_p, _i64, _p]),
     'dw_sgns_noise_alias': (ctypes.c_int, [_i64, _i32, _i32, _i64, _p, _u64, _u64, _p, _p]),
+    'dw_negative_edges': (ctypes.c_int, [_p, _p, _i64, _i64, _i64, _u64, _u64, _p, _p, _p]),
+    'dw_edge_features': (ctypes.c_int, [_p, _i64, _i32, _i32, _p, _i64, _p, _p, _p]),
+    'dw_edge_logreg_workspace_bytes': (ctypes.c_int, [_i64, _i32, _szp]),
+    'dw_edge_logreg': (ctypes.c_int, [_p, _i64, _i32, _i32, _p, _p, _i64, _p, _p, _p,
+                                      ctypes.c_size_t, _p, _p]),
     'dw_embedding_renorm_workspace_bytes': (ctypes.c_int, [_i64, _i64, _szp]),
     'dw_embedding_renorm': (ctypes.c_int, [_p, _i64, _i32, _p, _i64, _f64, _p, ctypes.c_size_t,
                                            _p, _p]),

@@ -220,6 +220,14 @@ class GraphDownstreamEdgeClassificationConfig:
     train_ratio: float = 0.5
     n_experiments: int = 10
     classifier_params: Optional[dict] = None
+    # 'sklearn': the reference's host path over a networkx graph; 'device': the CSR path of
+    # shallow_encoders/graph/linkpred.py (any graph dataset, graph_rmat included)
+    backend: str = 'sklearn'
+
+    def __post_init__(self):
+        if self.backend not in ('sklearn', 'device'):
+            raise ValueError(f'downstream.edge_classification.backend must be "sklearn" or '
+                             f'"device", got {self.backend!r}')
 
 
 @dataclass

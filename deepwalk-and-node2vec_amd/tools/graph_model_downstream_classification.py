@@ -15,7 +15,9 @@ tools/train.py) and runs the two tasks of the reference:
     (transductive, as the reference does).
 Negative pairs follow the reference's law: a uniform node, then a uniform node among its
 non-neighbours (itself included). sklearn's LogisticRegression with the config's
-``classifier_params``. The model only needs the checkpoint: no GPU is used here.
+``classifier_params``. The model only needs the checkpoint: no GPU is used here, unless
+``downstream.edge_classification.backend=device`` selects the device path for the edge task
+(shallow_encoders/graph/linkpred.py: the graph's CSR, so ``graph_rmat`` datasets work too).
 """
 import argparse
 import logging
@@ -165,6 +167,21 @@ def edge_classification(embeddings: np.ndarray, graph, stoi: Dict[str, int], tra
     return mean, best
 
 
+def edge_classification_on_device(embeddings: np.ndarray, graph, ec) -> Tuple[float, float]:
+    """``backend: device``: the same protocol over the graph's CSR (a networkx graph or a
+    ``CSRGraph``, so ``graph_rmat`` datasets too) with the table, the negative sampler and the
+    logistic regression on the GPU (shallow_encoders/graph/linkpred.py)."""
+    import torch
+    from shallow_encoders import _native
+    from shallow_encoders.graph import linkpred
+    from shallow_encoders.graph.random_walk_generator import _csr_of
+    dev = _native.require_device(None)
+    table = torch.from_numpy(np.ascontiguousarray(embeddings, dtype=np.float32)).to(dev)
+    return linkpred.edge_classification_device(
+        table, _csr_of(graph), ec.train_ratio, ec.n_experiments, ec.operator_name,
+        classifier_params=ec.classifier_params, device=dev)
+
+
 def load_input_embeddings(cfg, dataset, checkpoint_path: str) -> np.ndarray:
     """Input-embedding table of a tools/train.py checkpoint (weights-only load)."""
     import torch
@@ -209,7 +226,10 @@ def main(argv=None) -> Dict[str, float]:
             nc.n_experiments, features=dataset.features if dataset.has_features else None,
             classifier_params=nc.classifier_params, plot_path=plot)
     ec = cfg.downstream.edge_classification
-    if ec.enable:
+    if ec.enable and ec.backend == 'device':
+        result['edge_accuracy'], result['edge_best'] = edge_classification_on_device(
+            emb, dataset.graph, ec)
+    elif ec.enable:
         result['edge_accuracy'], result['edge_best'] = edge_classification(
             emb, dataset.graph, dataset.vocab.get_stoi(), ec.train_ratio, ec.n_experiments,
             ec.operator_name, classifier_params=ec.classifier_params)

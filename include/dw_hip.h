@@ -704,6 +704,50 @@ int dw_sgns_noise_alias(int64_t batch, int32_t n_ctx, int32_t neg_samples, int64
                         const uint64_t *table, uint64_t seed, uint64_t noise_offset,
                         int64_t *noise, void *stream);
 
+/* ---- link prediction on the device (shallow_encoders/graph/linkpred.py) ---------------------
+ * The reference's link-prediction protocol (tools/graph_model_downstream_classification.py:
+ * 170-200, 241-299) with everything that scales with the edge count on the device.
+ *
+ * dw_negative_edges: pairs int64[n, 2] of non-adjacent nodes under the reference's law
+ * (tools/graph_model_downstream_classification.py:170-200: u uniform over the nodes, v uniform
+ * over the nodes not adjacent to u, u itself allowed), without rejection. The nodes are rows
+ * first_node .. n_rows - 1 (first_node = 1 in the package: row 0 is <unk>), Nn = n_rows -
+ * first_node. Sample i, g = offset + i, draws philox<10>({lo(g), hi(g), 0, 'LP' << 16}, seed lo,
+ * seed hi): u = first_node + bounded64(x, y, Nn), m = Nn - deg(u), k = bounded64(z, w, m), and
+ * with c u's row of col_sorted (dw_csr_sort_copy) v = first_node + k + j, j the smallest index
+ * with c[j] - first_node - j > k (deg(u) when there is none): the k-th non-neighbour by rank, one
+ * binary search. Needs distinct neighbours per row (dw_csr_check_simple) and no neighbour below
+ * first_node; m <= 0 sets DW_S_BAD_CSR and writes (u, u). */
+int dw_negative_edges(const int64_t *row_ptr, const int32_t *col_sorted, int64_t n_rows,
+                      int64_t first_node, int64_t n, uint64_t seed, uint64_t offset,
+                      int64_t *pairs, int32_t *status, void *stream);
+
+/* out float[n, dim] = op(table[pairs[i, 0]], table[pairs[i, 1]]) — edge_operators.edge_embeddings
+ * (shallow_encoders/graph/edge_operators.py:5-55) on float32 rows: op 0 average (a + b) * 0.5f,
+ * 1 hadamard a * b, 2 weighted_l1 fabsf(a - b), 3 weighted_l2 (a - b) * (a - b), each in fp32 in
+ * exactly that operation order (no contraction). 1 <= dim <= 512; 16-B accesses when dim % 4 == 0
+ * and table and out are 16-B aligned. An id outside [0, vocab_size) sets DW_S_BAD_INDEX and its
+ * row is written as zeros (nothing out of range is read). */
+int dw_edge_features(const float *table, int64_t vocab_size, int32_t dim, int32_t op,
+                     const int64_t *pairs, int64_t n, float *out, int32_t *status, void *stream);
+
+/* One pass of a logistic regression over n labelled pairs, no feature stored — the loss,
+ * gradient and accuracy sklearn's LogisticRegression.fit / .score compute from the feature
+ * matrix of tools/graph_model_downstream_classification.py:241-299. coef double[dim + 1]
+ * (weights, then intercept; DEVICE memory), labels uint8[n] (non-zero = positive). Per sample:
+ * x = op(a, b) in fp32 as dw_edge_features; in float64 z = w . x + b0,
+ * loss = log1p(exp(-|z|)) + max(z, 0) - y z, r = 1 / (1 + exp(-z)) - y. out double[dim + 3]:
+ * [0, dim) = sum r x, [dim] = sum r, [dim + 1] = sum loss, [dim + 2] = #{(z > 0) == y}. All sums
+ * float64 and reproducible bit for bit: per-block partial rows in the workspace
+ * (>= dw_edge_logreg_workspace_bytes(n, dim)) added in block order by a second kernel, a grid
+ * that depends on (n, dim) and the table's 16-B alignment only, no float atomics. An id outside
+ * [0, vocab_size) sets DW_S_BAD_INDEX and counts as x = 0. n = 0 writes nothing. */
+int dw_edge_logreg_workspace_bytes(int64_t n, int32_t dim, size_t *bytes);
+int dw_edge_logreg(const float *table, int64_t vocab_size, int32_t dim, int32_t op,
+                   const int64_t *pairs, const uint8_t *labels, int64_t n, const double *coef,
+                   double *out, void *workspace, size_t workspace_bytes, int32_t *status,
+                   void *stream);
+
 /* nn.Embedding(max_norm=...) lookup side effect (model.py:24-25 with max_norm set; torch
  * embedding_renorm_): every DISTINCT row among ids[0..n_ids) whose L2 norm exceeds max_norm is
  * scaled by max_norm / (norm + 1e-7), in place. Ids are deduplicated on the device (radix sort
