@@ -38,7 +38,7 @@ DW_EXACT_ADAM = 2
 DW_METHOD_DEEPWALK = 0
 DW_METHOD_NODE2VEC = 1
 
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 _p = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -153,6 +153,9 @@ SIGNATURES = {
                                      _f32, _i32, _p]),
     'dw_adam_dense_to': (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, _f32, _f32, _f32, _f32, _f32,
                                          _f32, _f32, _i32, _i64, _p]),
+    'dw_sgd_dense': (ctypes.c_int, [_p, _p, _p, _i64, _f32, _f32, _f32, _f32, _i32, _i32, _i32,
+                                    _p]),
+    'dw_sgd_rows': (ctypes.c_int, [_p, _p, _i64, _i32, _p, _i32, _i64, _p, _f32, _p, _p]),
     'dw_scale': (ctypes.c_int, [_p, _i64, _f32, _p, _p]),
     'dw_step_scalars_bind': (ctypes.c_int, [_p]),
     'dw_step_scalars_bind_at': (ctypes.c_int, [_p, _i64]),

@@ -21,7 +21,8 @@ MI355X additions (all optional, defaulted, so reference configs load as they are
                           drawn once per walk (noise 'device' or 'unigram'), the step one MFMA
                           kernel (dw_sgns_walks_shared) and the optimizer's dense Adam; a departure
                           from the reference's negatives per pair
-``_target_: torch.optim.Adam`` instantiates the HIP Adam (word2vec/optim.py, same math).
+``_target_: torch.optim.Adam`` instantiates the HIP Adam and ``_target_: torch.optim.SGD`` the HIP
+SGD (word2vec/optim.py, same math).
 """
 import copy
 import dataclasses
@@ -44,6 +45,7 @@ logger = logging.getLogger('ConfigParser')
 # reference `_target_`s whose MI355X-native equivalent is substituted at instantiation
 TARGET_SUBSTITUTES = {
     'torch.optim.Adam': 'shallow_encoders.word2vec.optim.Adam',
+    'torch.optim.SGD': 'shallow_encoders.word2vec.optim.SGD',
 }
 
 

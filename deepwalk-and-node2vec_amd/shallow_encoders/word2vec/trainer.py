@@ -30,6 +30,13 @@ The optimizer's ``step()`` that follows is then a no-op for the two tables (Adam
 Same update as SGNS + ``optimizer.step()`` up to float-atomic summation order
 (test_gpu_trainer.py::test_fused_trainer_step_equals_unfused).
 
+SGD touched-rows step (``manual_grads`` + walk batches + the HIP SGD holding exactly the two
+tables with momentum = weight_decay = 0): the SGNS kernels accumulate the gradient as in the
+unfused step, then ``training_step`` steps the rows the batch lists and nothing else
+(_sgd_walk_step; exact, since plain SGD leaves a row without a gradient where it is), or the
+whole table where the batch lists at least as many ids as the table has rows. The optimizer's
+``step()`` that follows skips the two tables. Refuses the deterministic mode.
+
 Noise: ``noise='torch'`` draws the reference's uniform negatives with torch's global CPU
 generator (generate_noise_batch, exact under ``torch.manual_seed``); ``noise='device'`` draws
 the same law on the device (Philox keyed by ``seed`` and the running centre counter).
@@ -124,6 +131,7 @@ class Word2VecTrainer(_Base):
         self.logged: Dict[str, object] = {}
         self._side = None          # side stream of the fused step (input-table Adam)
         self._row_flags = None     # fused output-table Adam scratch
+        self._sgd_claim = None     # claim bitmap of the SGD touched-rows step (both tables)
         # set while word2vec/graphed.py GraphedTrainerStep captures the step: the steps add
         # their loss sums here and skip the per-step metrics (read once per replay), and
         # _capture_scatter = 'atomic' takes the atomic output-table scatter (tiny batches)
@@ -329,6 +337,13 @@ class Word2VecTrainer(_Base):
                 p.grad = torch.zeros_like(p)
             if isinstance(self._optimizer, Adam):
                 self._optimizer.mark_grads(fresh, True)
+            sgd_touched = targets is None and self._capture_acc is None and \
+                self._can_sgd_touched(w_in, w_out)
+            if sgd_touched and exact.enabled():
+                raise NotImplementedError(
+                    'the SGD touched-rows step has no deterministic mode (DW_DETERMINISTIC=1): '
+                    'it steps the float gradient buffers, which the fixed-point accumulators '
+                    'replace; use the HIP Adam, or SGD with momentum or weight decay')
             if exact.enabled():   # int64 fixed-point accumulators for the two gradient buffers
                 if self._exact is None:
                     self._exact = exact.Registry()
@@ -341,6 +356,8 @@ class Word2VecTrainer(_Base):
             if targets is None and self._capture_scatter != 'atomic' and \
                     self._can_fuse_step(w_in, w_out, C):
                 acc = self._fused_walk_step(w_in, w_out, src, R, noise, offset)
+            elif sgd_touched:
+                acc = self._sgd_walk_step(w_in, w_out, src, R, noise, offset)
             elif targets is None:
                 acc = sgns_accumulate(w_in.detach(), w_out.detach(), w_in.grad, w_out.grad,
                                       self._neg_samples, walks=src, context_radius=R, noise=noise,
@@ -416,6 +433,56 @@ class Word2VecTrainer(_Base):
         opt.swap_alt(w_in)
         return acc
 
+    # ---- SGD touched-rows step ------------------------------------------------------------------
+    def _can_sgd_touched(self, w_in, w_out) -> bool:
+        from shallow_encoders.word2vec.optim import SGD
+        opt = self._optimizer
+        return (isinstance(opt, SGD) and w_in.device.type == 'cuda'
+                and w_in.shape[0] < 2 ** 31 and opt.can_step_touched([w_in, w_out]))
+
+    def _sgd_buffer(self, key: tuple, shape: tuple, dtype, dev: torch.device) -> torch.Tensor:
+        """A persistent id buffer of the SGD step, as _unigram_noise keeps its negatives:
+        allocated on the first step of a shape."""
+        buf = self._noise_bufs.pop(key, None)
+        if buf is None or buf.device != dev:
+            buf = torch.empty(shape, dtype=dtype, device=dev)
+            while len(self._noise_bufs) >= self.NOISE_BUFFERS:   # the least recently used
+                self._noise_bufs.pop(next(iter(self._noise_bufs)))
+        self._noise_bufs[key] = buf
+        return buf
+
+    def _sgd_walk_step(self, w_in, w_out, walks, R: int, noise, offset: int) -> torch.Tensor:
+        """Plain SGD (module docstring of word2vec/optim.py): the gradient by the unchanged SGNS
+        kernels, then the update of the rows the batch lists — the centre columns for the input
+        table, every walk node and every negative for the output table (a superset of the rows
+        with a gradient: a window's targets are walk nodes). The optimizer picks rows or dense
+        per table from the id counts (optim.rows_apply); its ``step()`` then skips both tables.
+        Both updates run on the step's stream, one after the other: at C3's 64-walk shape the two
+        take 0.18 ms together, and no side-stream form was measured."""
+        opt = self._optimizer
+        dev = w_in.device
+        K = self._neg_samples
+        V = w_in.shape[0]
+        n, L = walks.shape
+        n_centres, C = n * (L - 2 * R), 2 * R
+        if noise is None:   # noise='device': the ids the kernels would draw, materialised once
+            noise = device_noise(n_centres, C, K, self._vocab_size, self._seed, offset, dev,
+                                 out=self._sgd_buffer(('sgd-noise', n_centres, C),
+                                                      (n_centres, C, K), torch.int64, dev))
+        acc = sgns_accumulate(w_in.detach(), w_out.detach(), w_in.grad, w_out.grad, K,
+                              walks=walks, context_radius=R, noise=noise, seed=self._seed,
+                              noise_offset=offset)
+        centres = self._sgd_buffer(('sgd-centres', n, L - 2 * R), (n, L - 2 * R), torch.int32,
+                                   dev)
+        centres.copy_(walks[:, R:L - R])
+        words = (V + 31) // 32
+        if self._sgd_claim is None or self._sgd_claim.numel() != words or \
+                self._sgd_claim.device != dev:   # the claim bitmap: zero between rows steps
+            self._sgd_claim = torch.zeros(words, dtype=torch.int32, device=dev)
+        opt.step_touched(w_in, [centres], self._sgd_claim)
+        opt.step_touched(w_out, [walks, noise.contiguous()], self._sgd_claim)
+        return acc
+
     def push_replayed(self, terms: Dict[str, torch.Tensor], n_steps: int) -> Dict[str, torch.Tensor]:
         """The metrics of ``n_steps`` graph-replayed steps (word2vec/graphed.py
         GraphedTrainerStep): their mean loss terms stand for each of the steps in the epoch
@@ -435,6 +502,8 @@ class Word2VecTrainer(_Base):
         st = getattr(self, '_renorm_status', None)
         if st is not None:
             _native.check_status(st, 'max_norm renormalisation')
+        if hasattr(self._optimizer, 'check_status'):   # the HIP SGD's rows steps
+            self._optimizer.check_status()
         if self._meter.is_empty:
             return {}
         out = {}

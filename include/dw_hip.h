@@ -823,6 +823,43 @@ int dw_adam_dense_to(const float *param_src, float *param_dst, float *grad, floa
                      float eps, float weight_decay, int32_t zero_grad, int64_t max_blocks,
                      void *stream);
 
+/* Dense SGD step, torch.optim.SGD single-tensor semantics (torch/optim/sgd.py:_single_tensor_sgd,
+ * maximize=False), for configs whose `train.optimizer._target_` names it (the reference's
+ * config_parser/core.py:43-53 instantiates whatever optimizer the config names). The host
+ * prepares the scalars in float64 and casts them to float32: neg_lr = -lr, weight_decay,
+ * momentum, one_minus_dampening = 1 - dampening. Per element, every fma a single rounding:
+ *   g1  = weight_decay != 0 ? fma(weight_decay, p, g) : g
+ *   buf = first_step ? g1 : fma(one_minus_dampening, g1, RN(momentum * buf))   (momentum != 0)
+ *   g2  = momentum == 0 ? g1 : nesterov ? fma(momentum, buf, g1) : buf
+ *   p   = fma(neg_lr, g2, p)
+ * which is torch's update on CPU fp32 tensors bit for bit (tests/test_sgd.py).
+ * momentum_buf: NULL iff momentum == 0 (torch's state `momentum_buffer`; first_step != 0 writes
+ * it without reading it). zero_grad != 0 also writes g = 0 in the same pass. One streaming pass,
+ * 16-B accesses where the buffers are 16-B aligned, any n_elem >= 0. */
+int dw_sgd_dense(float *param, float *grad, float *momentum_buf, int64_t n_elem, float neg_lr,
+                 float weight_decay, float momentum, float one_minus_dampening, int32_t nesterov,
+                 int32_t first_step, int32_t zero_grad, void *stream);
+
+/* Plain SGD (momentum = weight_decay = 0) over the rows a batch touched: for every distinct row r
+ * in ids, p[r] = fma(neg_lr, g[r], p[r]) and g[r] = 0 (the arithmetic of dw_sgd_dense, the same
+ * bits). A row with g = 0 does not move under plain SGD, so with ids a superset of the rows that
+ * hold a gradient this is the whole step, with nothing dense in it.
+ *   param, grad: float32 [n_table_rows, dim], dim >= 1 (rows are stepped with the widest of
+ *         16-, 8- and 4-B accesses that dim and the buffers' alignment keep aligned for every row);
+ *   ids:  n_ids row ids, int32 (id_bytes 4) or int64 (id_bytes 8), in any order, duplicates in
+ *         any number: each distinct row is stepped once. An id outside [0, n_table_rows) is
+ *         skipped and sets DW_S_BAD_INDEX in status;
+ *   claim: uint32 [ceil(n_table_rows / 32)], all zero on entry and left all zero (cleared on the
+ *         stream behind the step): one bit per row, taken by the first lister of the row;
+ *   neg_lr = -lr <= 0.
+ * A row not listed keeps its p and g bit for bit; so does a listed row whose gradient is all +0
+ * (nothing is written for it). Two launches (the step, the bitmap clear) whose geometry depends
+ * only on (n_ids, n_table_rows, dim); no synchronisation, no allocation, no host read: the call
+ * can be captured in a HIP graph. n_ids == 0 is a no-op. */
+int dw_sgd_rows(float *param, float *grad, int64_t n_table_rows, int32_t dim, const void *ids,
+                int32_t id_bytes, int64_t n_ids, uint32_t *claim, float neg_lr, int32_t *status,
+                void *stream);
+
 /* Scale a float32 buffer in place: x *= alpha * (*alpha_dev) (alpha_dev NULL -> 1). Used by the
  * autograd path to apply the device-resident grad_output without a host synchronisation. */
 /* Lazy exact Adam over selected rows (OwnerLazyTables, the touched-row in-table exchange;
