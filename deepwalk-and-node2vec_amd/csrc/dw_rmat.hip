@@ -20,6 +20,7 @@
 #include <rocprim/iterator/counting_iterator.hpp>
 
 #include "dw_common.h"
+#include "dw_ingest.h"
 
 namespace {
 
@@ -147,24 +148,9 @@ __global__ void k_row_ptr_head(int64_t *row_ptr) {
     row_ptr[1] = 0;
 }
 
-inline size_t a256(size_t x) { return (x + 255) & ~size_t(255); }
-
-int bits_for(int64_t n) {  // bits of values < n
-    int b = 1;
-    while (b < 63 && (static_cast<uint64_t>(n - 1) >> b) != 0) ++b;
-    return b;
-}
-
-inline unsigned grid_of(int64_t n) { return static_cast<unsigned>((n + 255) / 256); }
-
-#define DW_HIP_OK(expr, what)                                                       \
-    do {                                                                            \
-        hipError_t e_ = (expr);                                                     \
-        if (e_ != hipSuccess) {                                                     \
-            ::dw::set_error("%s: %s", what, hipGetErrorString(e_));                 \
-            return DW_E_HIP;                                                        \
-        }                                                                           \
-    } while (0)
+using dw::ingest::a256;   // (shared with dw_edgelist.hip: dw_ingest.h)
+using dw::ingest::bits_for;
+using dw::ingest::grid_of;
 
 // ---- workspace plans (one size serves the three calls) ----------------------------------------
 struct RmatPlan {

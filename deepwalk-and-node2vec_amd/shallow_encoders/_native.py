@@ -32,13 +32,14 @@ DW_S_BAD_INDEX = 16
 DW_S_RECORDS_FULL = 32
 DW_S_DUP_NEIGHBOR = 64
 DW_S_FIXED_RANGE = 128
+DW_S_BAD_TEXT = 256
 DW_EXACT_DEFER = 1
 DW_EXACT_ADAM = 2
 
 DW_METHOD_DEEPWALK = 0
 DW_METHOD_NODE2VEC = 1
 
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 _p = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -73,6 +74,13 @@ SIGNATURES = {
                                      ctypes.c_size_t, _p]),
     'dw_graph_isolated': (ctypes.c_int, [_p, _i64, _i64, _p, _p, _p, _p, ctypes.c_size_t, _p]),
     'dw_csr_from_edges': (ctypes.c_int, [_p, _i64, _i64, _p, _p, _p, _p, ctypes.c_size_t, _p]),
+    'dw_edgelist_workspace_bytes': (ctypes.c_int, [_i64, _i64, _szp]),
+    'dw_edgelist_parse': (ctypes.c_int, [_p, _i64, _i64, _p, _p, _i64, _p, _p, _p, _p,
+                                         ctypes.c_size_t, _p]),
+    'dw_edges_canonical': (ctypes.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _p, _p, _p, _p,
+                                          ctypes.c_size_t, _p]),
+    'dw_csr_from_edges_loops': (ctypes.c_int, [_p, _p, _i64, _i64, _p, _p, _p, _p, _p,
+                                               ctypes.c_size_t, _p]),
     'dw_walk_replay': (ctypes.c_int, [_p, _p, _p, _p, _i64, _p, _i64, _i32, _i32, _f64, _f64,
                                       _p, _p, _p, _p]),
     'dw_walk_fast': (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, _p, _i64, _i32, _i32, _f64, _f64,
@@ -286,4 +294,6 @@ def check_status(status: torch.Tensor, what: str) -> None:
     if s & DW_S_FIXED_RANGE:
         raise OverflowError(f'{what}: a gradient term exceeded the deterministic mode\'s '
                             f'fixed-point range (|term| * 2^frac >= 2^51)')
+    if s & DW_S_BAD_TEXT:
+        raise ValueError(f'{what}: malformed edge-list line')
     raise RuntimeError(f'{what}: device status {s:#x}')

@@ -300,7 +300,7 @@ def unigram_weights(dataset) -> torch.Tensor:
                          'for a text dataset construct Word2VecTrainer(noise="unigram", '
                          'noise_weights=<count per vocabulary id>) yourself')
     deg = np.diff(csr.row_ptr)
-    if csr.weights is None:
+    if not csr.weighted:
         return torch.from_numpy(deg.astype(np.float64))
     rows = np.repeat(np.arange(len(deg)), deg)
     return torch.from_numpy(np.bincount(rows, weights=csr.weights, minlength=len(deg)))

@@ -71,16 +71,65 @@ class NodeNames(Sequence):
         return int(m.group(1)) + 1
 
 
+class IdNames(Sequence):
+    """``['<unk>', 'n0000003', 'n0000017', ...]`` over a sorted array of distinct integer ids
+    (edge-list graphs, graph/edge_list.py): vocabulary id i + 1 is named ``n`` + ids[i] zero-padded
+    to ``width``, so lexicographic order is numeric order. Like NodeNames it holds no list of
+    strings; ``index`` is a binary search and rejects a token that is not one of the ids."""
+
+    def __init__(self, ids: np.ndarray, width: Optional[int] = None):
+        self.ids = np.ascontiguousarray(ids, dtype=np.int64)
+        if len(self.ids) and (self.ids[0] < 0 or np.any(np.diff(self.ids) <= 0)):
+            raise ValueError('IdNames needs distinct non-negative ids in increasing order')
+        self.width = int(width) if width is not None else id_name_width(
+            int(self.ids[-1]) if len(self.ids) else 0)
+
+    def __len__(self) -> int:
+        return len(self.ids) + 1
+
+    def _name(self, i: int) -> str:
+        return UNK if i == 0 else f'n{int(self.ids[i - 1]):0{self.width}d}'
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self._name(j) for j in range(*i.indices(len(self)))]
+        if i < 0:
+            i += len(self)
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        return self._name(i)
+
+    def index(self, token, *args) -> int:
+        if token == UNK:
+            return 0
+        m = re.fullmatch(r'n(\d+)', str(token))
+        if m is not None and len(m.group(1)) == self.width:
+            v = int(m.group(1))
+            k = int(np.searchsorted(self.ids, v))
+            if k < len(self.ids) and int(self.ids[k]) == v:
+                return k + 1
+        raise ValueError(f'{token!r} is not a node name')
+
+
+def id_name_width(max_id: int) -> int:
+    """Digits of an edge-list graph's node names: at least 7 (rmat.name_width's floor)."""
+    return max(7, len(str(int(max_id))))
+
+
+LAZY_NAMES = (NodeNames, IdNames)
+
+
 @dataclass
 class CSRGraph:
     """Host (numpy) CSR plus lazily built device copies."""
     row_ptr: np.ndarray                 # int64 [V+1]
     col: np.ndarray                     # int32 [nnz]
-    weights: Optional[np.ndarray]       # float64 [nnz] or None
+    weights: Optional[np.ndarray]       # float64 [nnz] or None (a property: see _weights_get)
     itos: List[str]                     # vocabulary (id -> token), itos[0] == '<unk>'
     names: List[object]                 # id -> original node object (None for <unk>)
     _dev: Dict[str, torch.Tensor] = field(default_factory=dict, repr=False)
     _dev_device: Optional[torch.device] = field(default=None, repr=False)
+    _dev_weighted: bool = field(default=False, repr=False)   # device-built with weights
 
     # ------------------------------------------------------------------ construction
     @staticmethod
@@ -129,23 +178,26 @@ class CSRGraph:
         if itos is None:
             width = max(7, len(str(V - 1)))
             itos = [UNK] + [f'n{i:0{width}d}' for i in range(V - 1)]
-        if not isinstance(itos, NodeNames):
+        if not isinstance(itos, LAZY_NAMES):
             itos = list(itos)
         if names is None:
-            names = itos if isinstance(itos, NodeNames) else [None] + itos[1:]
+            names = itos if isinstance(itos, LAZY_NAMES) else [None] + itos[1:]
         if len(itos) != V:
             raise ValueError('itos length must equal the number of CSR rows')
         return CSRGraph(row_ptr, col, weights, itos,
-                        names if isinstance(names, NodeNames) else list(names))
+                        names if isinstance(names, LAZY_NAMES) else list(names))
 
     @staticmethod
-    def from_device(row_ptr: torch.Tensor, col: torch.Tensor, itos: Sequence[str]) -> 'CSRGraph':
-        """A CSR built in HBM (dw_csr_from_edges): row_ptr is copied to the host (V+1 int64),
-        col stays on the device only (``col`` is None until ``host_col()``)."""
+    def from_device(row_ptr: torch.Tensor, col: torch.Tensor, itos: Sequence[str],
+                    weights: Optional[torch.Tensor] = None) -> 'CSRGraph':
+        """A CSR built in HBM (dw_csr_from_edges, dw_csr_from_edges_loops): row_ptr is copied to
+        the host (V+1 int64), col and the optional float64 weights stay on the device only
+        (``col`` is None until ``host_col()``; ``weights`` downloads itself when first read)."""
         g = CSRGraph(row_ptr.cpu().numpy(), None, None, itos, itos)
         g._dev_device = col.device
-        g._dev = {'row_ptr': row_ptr, 'col': col, 'weights': None,
+        g._dev = {'row_ptr': row_ptr, 'col': col, 'weights': weights,
                   'status': torch.zeros(1, dtype=torch.int32, device=col.device)}
+        g._dev_weighted = weights is not None
         return g
 
     def host_col(self) -> np.ndarray:
@@ -153,6 +205,16 @@ class CSRGraph:
         if self.col is None:
             self.col = self._dev['col'].cpu().numpy()
         return self.col
+
+    def _weights_get(self) -> Optional[np.ndarray]:
+        w = self.__dict__.get('weights')
+        if w is None and self._dev_weighted:   # device-built: downloaded once, when first read
+            w = self._dev['weights'].cpu().numpy()
+            self.__dict__['weights'] = w
+        return w
+
+    def _weights_set(self, value) -> None:
+        self.__dict__['weights'] = value
 
     # ------------------------------------------------------------------ host helpers
     @property
@@ -165,7 +227,8 @@ class CSRGraph:
 
     @property
     def weighted(self) -> bool:
-        return self.weights is not None
+        """Whether the graph carries weights (no download for a device-built graph)."""
+        return self.__dict__.get('weights') is not None or self._dev_weighted
 
     def degree(self) -> np.ndarray:
         return np.diff(self.row_ptr)
@@ -178,7 +241,7 @@ class CSRGraph:
 
     def node_id(self, node) -> int:
         tok = node_token(node)
-        if isinstance(self.itos, NodeNames):
+        if isinstance(self.itos, LAZY_NAMES):
             return self.itos.index(tok)
         sto = self.__dict__.setdefault('_stoi_cache', None)
         if sto is None:
@@ -200,6 +263,8 @@ class CSRGraph:
         if self._dev_device != dev:
             if self.col is None and 'col' in self._dev:   # device-built: keep a host copy
                 self.col = self._dev['col'].cpu().numpy()
+            if self._dev_weighted:
+                self._weights_get()   # (downloads them: the old device's copy is about to go)
             self._dev = {}
             self._dev_device = dev
         d = self._dev
@@ -216,7 +281,7 @@ class CSRGraph:
             _native.check_status(st, 'CSR validation')
         if need_sorted and 'col_sorted' not in d:
             d['col_sorted'] = self._sorted_copy(dev)
-        if need_alias and self.weights is not None and 'prob_thr' not in d:
+        if need_alias and self.weighted and 'prob_thr' not in d:
             self._build_alias(dev)
         if need_edges and 'edges' not in d:
             self._build_edges(dev)
@@ -278,7 +343,7 @@ class CSRGraph:
             raise RuntimeError('the Philox node2vec walker is chosen (and its index built) '
                                'before a graph capture: walk once first')
         use = False
-        if self.weights is None and self.is_simple(dev) and 16 * (self.nnz + 1) <= \
+        if not self.weighted and self.is_simple(dev) and 16 * (self.nnz + 1) <= \
                 self.N2V_PHILOX_INDEX_BYTES:
             info = d.get('n2v_index_info') or {}
             if 'bytes' not in info:   # the size is known once the offsets have been scanned
@@ -295,7 +360,7 @@ class CSRGraph:
         when the device cannot hold it, ValueError on a weighted graph or a repeated
         neighbour."""
         dev = _native.require_device(device)
-        if self.weights is not None:
+        if self.weighted:
             raise ValueError('the node2vec position index needs an unweighted graph')
         self.require_simple(dev)
         d = self.device_tensors(dev)
@@ -551,3 +616,8 @@ class CSRGraph:
                          _native.ptr(d['alias']), _native.ptr(work_p), _native.ptr(work_i),
                          _native.ptr(st), _native.stream(dev))
         _native.check_status(st, 'alias build')
+
+
+# ``weights`` stays a dataclass field (constructor, repr, equality) and reads through a property:
+# a graph built on the device with weights downloads them only when the host first asks.
+CSRGraph.weights = property(CSRGraph._weights_get, CSRGraph._weights_set)

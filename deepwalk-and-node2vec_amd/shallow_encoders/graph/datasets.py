@@ -271,3 +271,28 @@ class RMATDataset(RandomWalkDataset):
         graph = rmat_graph(scale, n_edges, graph_seed)
         super().__init__(graph=graph, walks_per_node=walks_per_node, walk_length=walk_length,
                          method=method, **kwargs)
+
+
+@register_dataset('graph_edge_list')
+class EdgeListDataset(RandomWalkDataset):
+    """A user's graph from an edge-list file (graph/edge_list.py: SNAP / OGB-style text or CSV,
+    ``.npy``, ``.npz``), built straight to CSR (no networkx).
+
+    ``build``: 'host' (numpy), 'device' (parsed and built in HBM) or 'auto' (device when one is
+    visible); both give the same arrays. ``skip_rows`` drops header lines of a text file.
+    """
+
+    def __init__(self, walks_per_node: int, walk_length: int, method: str = 'deepwalk',
+                 path: Optional[str] = None, skip_rows: int = 0, build: str = 'auto',
+                 **kwargs):
+        from shallow_encoders.graph.edge_list import read_edge_list
+        if path is None:
+            raise ValueError('graph_edge_list needs the edge-list file: set '
+                             'datamodule.additional_parameters.path=<file>')
+        if build not in ('auto', 'host', 'device'):
+            raise ValueError(f'build must be auto, host or device, got {build!r}')
+        on_device = build == 'device' or (build == 'auto' and torch.cuda.is_available())
+        device = (kwargs.get('device') or 'cuda') if on_device else None
+        graph = read_edge_list(os.path.expanduser(path), device=device, skip_rows=skip_rows)
+        super().__init__(graph=graph, walks_per_node=walks_per_node, walk_length=walk_length,
+                         method=method, **kwargs)

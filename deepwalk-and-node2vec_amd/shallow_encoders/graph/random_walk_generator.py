@@ -90,7 +90,7 @@ def sum_is_exact(csr: CSRGraph, inv_p: float, inv_q: float, node2vec: bool) -> b
         return False
     row_ptr = np.asarray(csr.row_ptr, dtype=np.int64)
     deg = np.diff(row_ptr)
-    if csr.weights is None:
+    if not csr.weighted:
         terms = np.asarray(factors, dtype=np.float64)
         k = _dyadic_scale(terms)
         bound = float(deg.max(initial=0)) * float(terms.max()) * 2.0 ** k
@@ -188,7 +188,7 @@ class RandomWalk(ABC):
     def get_node_unnormalized_edge_weights(self, node) -> List[float]:
         i = self._csr.node_id(node)
         a, b = self._csr.row_ptr[i], self._csr.row_ptr[i + 1]
-        if self._csr.weights is None:
+        if not self._csr.weighted:
             return [1 for _ in range(a, b)]
         return [float(w) for w in self._csr.weights[a:b]]
 
@@ -234,11 +234,11 @@ class RandomWalk(ABC):
         # replay, DeepWalk on an unweighted graph: the same walks over the edge-inline CSR
         # (dw_walk_replay_inline; layout='csr' keeps dw_walk_replay)
         replay_inline = (self._rng == 'python' and not n2v and self._layout == 'indexed'
-                         and self._csr.weights is None)
+                         and not self._csr.weighted)
         # replay, node2vec on an unweighted graph: the adjacency-hash replay (dw_walk_replay_
         # indexed: the shorter list of each step probed; the same walks as dw_walk_replay)
         replay_n2v_idx = (self._rng == 'python' and n2v and self._layout == 'indexed'
-                          and self._csr.weights is None)
+                          and not self._csr.weighted)
         d = self._csr.device_tensors(dev, need_sorted=n2v and not indexed,
                                      need_alias=self._rng == 'philox',
                                      need_edges=(indexed and not n2v) or replay_inline,
@@ -340,7 +340,7 @@ class RandomWalk(ABC):
         position index: 'probes' counts the picks made by the serial arithmetic, 'entries' the
         2-B position units read, 'lines' the searches' dependent 128-B line moves)."""
         if self.METHOD != _native.DW_METHOD_NODE2VEC or self._rng != 'python' \
-                or self._csr.weights is not None:
+                or self._csr.weighted:
             raise ValueError('count_replay_traffic: node2vec with rng="python", unweighted')
         dev = _native.require_device(self._device)
         starts = torch.as_tensor(start_ids, dtype=torch.int32).to(dev).contiguous()

@@ -50,6 +50,7 @@ extern "C" {
 #define DW_S_RECORDS_FULL   32   /* owner-form SGNS records exceeded the workspace (not expected)    */
 #define DW_S_DUP_NEIGHBOR   64   /* a CSR row lists a neighbour twice (dw_csr_check_simple)          */
 #define DW_S_FIXED_RANGE   128   /* a gradient term past the deterministic fixed-point range         */
+#define DW_S_BAD_TEXT      256   /* a line of an edge-list text is malformed (dw_edgelist_parse)     */
 
 #define DW_METHOD_DEEPWALK   0   /* random_walk_generator.py:56-72 ('deepwalk' and 'dfs')          */
 #define DW_METHOD_NODE2VEC   1   /* random_walk_generator.py:75-119                                  */
@@ -199,6 +200,47 @@ int dw_graph_isolated(const uint64_t *edges, int64_t n_edges, int64_t n_nodes,
 int dw_csr_from_edges(const uint64_t *edges, int64_t n_edges, int64_t n_nodes,
                       int64_t *row_ptr, int32_t *col, int32_t *status, void *workspace,
                       size_t workspace_bytes, void *stream);
+
+/* ---- Edge-list ingestion (shallow_encoders/graph/edge_list.py): a user's graph, as text or as
+ * id arrays, to the CSR of CSRGraph.from_networkx(nx.Graph().add_edges_from(...)) over names
+ * "n" + zero-padded id. One workspace size serves the three calls below (n_text_bytes: the
+ * largest text chunk, 0 without text; n_edges: the largest raw edge count). Every output is a
+ * pure function of the input (stable sorts, scans, selects, integer atomics only). */
+int dw_edgelist_workspace_bytes(int64_t n_text_bytes, int64_t n_edges, size_t *bytes);
+
+/* Parses text[0, n_bytes) (uint8, in HBM; no read goes past n_bytes), one edge per line: lines end
+ * in '\n' (a '\r' that closes the line is dropped, the last line may lack its '\n'); lines of
+ * blanks (space, tab) only, and lines whose first non-blank byte is '#' or '%', are skipped; a
+ * data line is blanks, 1-18 decimal digits, one or more of {space, tab, comma}, 1-18 digits,
+ * then the line's end or a separator followed by anything. Lines with index < skip_lines are
+ * dropped unparsed. Output: src, dst int64 [capacity] in file order (a data line past capacity
+ * sets DW_S_RECORDS_FULL; capacity (n_bytes + 1) / 4 always suffices), counts[0] = data lines,
+ * counts[1] = lines seen (device int64 [2]). Any other line sets DW_S_BAD_TEXT and
+ * *err_line (device int64) = the smallest such 0-based line index, else -1. */
+int dw_edgelist_parse(const uint8_t *text, int64_t n_bytes, int64_t skip_lines, int64_t *src,
+                      int64_t *dst, int64_t capacity, int64_t *counts, int64_t *err_line,
+                      int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Raw edges (src, dst int64 [n_edges], ids in [0, 2^id_bits), id_bits <= 60: others set
+ * DW_S_BAD_INDEX; weights float64 [n_edges] or NULL) to their canonical form: node_ids int64
+ * [<= 2 n_edges] = the distinct ids ascending (a node's rank is its index); edges uint64
+ * [<= n_edges] = every undirected pair once, rank(src) << 32 | rank(dst) in the orientation and
+ * at the position of its first occurrence; edge_weights float64 = the weight of the pair's last
+ * occurrence; counts[0] = nodes, counts[1] = unique edges (device int64 [2]). Self-loops kept. */
+int dw_edges_canonical(const int64_t *src, const int64_t *dst, const double *weights,
+                       int64_t n_edges, int32_t id_bits, int64_t *node_ids, uint64_t *edges,
+                       double *edge_weights, int64_t *counts, int32_t *status, void *workspace,
+                       size_t workspace_bytes, void *stream);
+
+/* dw_csr_from_edges for edges that may hold self-loops and carry weights: a self-loop is one
+ * entry and one degree (networkx lists it once); edge_weights float64 [n_edges] or NULL goes to
+ * both directions (weights float64 [2 n_edges]). row_ptr int64 [n_nodes + 2]; col int32
+ * [2 n_edges], of which row_ptr[n_nodes + 1] are written. Endpoints >= n_nodes set DW_S_BAD_CSR
+ * and their edge is left out. */
+int dw_csr_from_edges_loops(const uint64_t *edges, const double *edge_weights, int64_t n_edges,
+                            int64_t n_nodes, int64_t *row_ptr, int32_t *col, double *weights,
+                            int32_t *status, void *workspace, size_t workspace_bytes,
+                            void *stream);
 
 /* Exact replay walker — bit-exact with DeepWalk.walk / Node2Vec.walk
  * (random_walk_generator.py:61-72 / 94-119) given the uniforms random.random() would return.
