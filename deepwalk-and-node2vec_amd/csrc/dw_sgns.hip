@@ -21,8 +21,12 @@
 //     pass 2 (k_rec_gather) gathers the centre rows and sums every output row's records in
 //     registers. No float atomics except where a row straddles two fixed-size chunks; the
 //     gathered bytes move at read speed, not atomic speed.
+//     Walks forms: each walk position's positive terms (at most 2R centres of its own walk) are
+//     summed once by k_walk_agg and enter the sort and pass 2 as one aggregate record
+//     (walk_agg_active, plan_walks).
 #include <stdlib.h>
 
+#include <atomic>
 #include <cmath>
 #include <mutex>
 #include <unordered_map>
@@ -133,7 +137,15 @@ struct SgnsArgs {
     int64_t occ_per_wave;     //   occ[g * occ_per_wave, (g+1) * occ_per_wave)
     const dw_step_scalars *dyn;   // bound step block (graph replay): noise_offset from it
     dw::Fixed fx_in{};        // deterministic mode: g_in's int64 accumulator (dw_exact_register)
+    // walk aggregation (k_walk_agg): positive slot (b, jctx)'s coefficient goes to
+    // coef_pos[b * C + jctx], not into a record; the negatives' records are dense at
+    // [0, batch * C * K), the aggregate records follow; agg: [n_walks * L, d] aggregate rows
+    float *coef_pos = nullptr;
+    float *agg = nullptr;
 };
+
+// An aggregate record's centre field: bit 31 (free: the records mode needs V < 2^31) | w L + j.
+constexpr uint32_t AGG_BIT = 1u << 31;
 
 #ifndef DW_NOISE_ROUNDS
 #define DW_NOISE_ROUNDS 10  // (timing experiments only: any other value changes the stream)
@@ -389,10 +401,15 @@ __device__ __forceinline__ float row_sum16(float x) {
 // pre-step values p^{s-1} (k_out_rows leaves the rows it steps pending: m and v at step s, the
 // parameter half deferred): only the centre gradient is formed — the same FMAs in the same
 // order as the full pass.
-template <int F4, bool FROM_WALKS, int CHR, bool OWNER, bool EXACT = false, bool COEFIN = false>
+// AGG (walks, records, not OWNER, not EXACT; plan_walks): a positive slot's coefficient goes to
+// coef_pos[b C + jctx] and k_walk_agg sums each walk position's positive terms into one
+// aggregate row; only the negatives leave as records, dense at b C K + j K + k.
+template <int F4, bool FROM_WALKS, int CHR, bool OWNER, bool EXACT = false, bool COEFIN = false,
+          bool AGG = false>
 __global__ void __launch_bounds__(WAVES_PER_BLOCK *WAVE, CHR >= 8 ? 3 : G16_MIN_WAVES)
     k_sgns_g16(SgnsArgs a) {
     static_assert(!COEFIN || OWNER, "the coefficients-in form is the owner path's");
+    static_assert(!AGG || (FROM_WALKS && !OWNER && !EXACT), "aggregation: the float walks form");
     constexpr int D = 64 * F4;
     __shared__ int32_t s_id[WAVES_PER_BLOCK][4][G16_TMAX];
     __shared__ float s_coef[WAVES_PER_BLOCK][4][G16_TMAX];
@@ -680,6 +697,17 @@ __global__ void __launch_bounds__(WAVES_PER_BLOCK *WAVE, CHR >= 8 ? 3 : G16_MIN_
                 const int tt = gl + 16 * k;
                 if (tt < T) {
                     const int32_t id = s_id[wv][q][tt];
+                    if constexpr (AGG) {
+                        const int j = tt / rows_per_ctx, k = tt - j * rows_per_ctx - 1;
+                        if (k < 0) {   // (an invalid row's coefficient stayed 0)
+                            a.coef_pos[b * a.C + j] = s_coef[wv][q][tt];
+                        } else {
+                            const int64_t at = (b * a.C + j) * a.K + k;
+                            a.rec_key[at] = static_cast<uint32_t>(id < 0 ? 0 : id);
+                            a.rec_val[at] = pack_record(s_coef[wv][q][tt], ok_c ? cid : 0);
+                        }
+                        continue;
+                    }
                     a.rec_key[b * T + tt] = static_cast<uint32_t>(id < 0 ? 0 : id);
                     a.rec_val[b * T + tt] = pack_record(s_coef[wv][q][tt], ok_c ? cid : 0);
                 }
@@ -762,6 +790,91 @@ __global__ void __launch_bounds__(WAVES_PER_BLOCK *WAVE, CHR >= 8 ? 3 : G16_MIN_
             *a.count_out = static_cast<uint32_t>(a.batch * T);
     }
     if (a.loss_acc) flush_loss(a.loss_acc, acc_pos, acc_neg, acc_rec, acc_prec);
+}
+
+// Walk aggregation, after the AGG pass 1. Position j of walk w is the context of the centres i
+// with |i - j| <= R, i != j, R <= i < L - R — all in its own walk — so its positive out-gradient
+// terms sum to G[w][j] = sum_i coef(i, j) w_in[walk[w][i]]: at most 2R terms, formed here ONCE
+// as row w L + j of a.agg. The position then enters the sort and the gather as a single record
+// {key walk[w][j], coefficient 1, centre field AGG_BIT | (w L + j)} at rec[n_neg + w L + j]
+// (an id outside [0, V): key 0, coefficient 0, DW_S_BAD_INDEX) in place of its <= 2R positive
+// records: 2R (L - 2R) / L times fewer (8.75 at C3).
+// One block per (walk, SL-column slice): the slice of the walk's L - 2R centre rows and its
+// C (L - 2R) positive coefficients are staged in LDS (35 KB + 2.8 KB at C3); lane group t / LPR
+// takes positions r, r + RPP, ... and sums each element over its centres in ascending i with
+// fmaf — a fixed order, no atomics: agg is bit-reproducible given the coefficients. Rows leave
+// as coalesced float4 stores (512 B per row and slice).
+template <int SL>
+__global__ void __launch_bounds__(256) k_walk_agg(SgnsArgs a, int64_t n_neg) {
+    extern __shared__ float4 s_agg[];
+    constexpr int LPR = SL / 4;      // lanes per row, one float4 each
+    constexpr int RPP = 256 / LPR;   // rows per pass of the block
+    const int per = a.L - 2 * a.R;
+    float4 *s_row = s_agg;                                               // [per][LPR]
+    float *s_cf = reinterpret_cast<float *>(s_row + per * LPR);          // [per][C]
+    int32_t *s_pos = reinterpret_cast<int32_t *>(s_cf + per * a.C);      // [L]
+    const int64_t w = blockIdx.x;
+    const int col = blockIdx.y * SL + 4 * (threadIdx.x % LPR);
+    const int r = threadIdx.x / LPR, c = threadIdx.x % LPR;
+    const int32_t *walk = a.walks + w * a.L;
+    for (int j = threadIdx.x; j < a.L; j += 256) s_pos[j] = walk[j];
+    // the staging loads in batches of independent loads (one load, one LDS store at a time ran
+    // the block at the latency of ~20 dependent global loads: 203 us per call at C3)
+    constexpr int UC = 4, UR = 8;
+    const float *cf_in = a.coef_pos + w * per * a.C;
+    for (int k0 = threadIdx.x; k0 < per * a.C; k0 += UC * 256) {
+        float x[UC];
+#pragma unroll
+        for (int u = 0; u < UC; ++u) x[u] = k0 + u * 256 < per * a.C ? cf_in[k0 + u * 256] : 0.f;
+#pragma unroll
+        for (int u = 0; u < UC; ++u)
+            if (k0 + u * 256 < per * a.C) s_cf[k0 + u * 256] = x[u];
+    }
+    __syncthreads();   // (s_pos)
+    for (int c0 = r; c0 < per; c0 += UR * RPP) {
+        float4 x[UR];
+#pragma unroll
+        for (int u = 0; u < UR; ++u) {
+            const int ci = c0 + u * RPP;
+            // (a bad centre id reads nothing: pass 1 left its coefficients 0)
+            const int64_t id = ci < per ? s_pos[a.R + ci] : -1;
+            x[u] = (id >= 0 && id < a.V)
+                       ? *reinterpret_cast<const float4 *>(a.w_in + id * a.d + col)
+                       : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int u = 0; u < UR; ++u)
+            if (c0 + u * RPP < per) s_row[(c0 + u * RPP) * LPR + c] = x[u];
+    }
+    __syncthreads();
+    for (int j = r; j < a.L; j += RPP) {
+        // centres ci = i - R of position j: [j - 2R, j] inside [0, per), without i == j
+        const int lo = j - 2 * a.R > 0 ? j - 2 * a.R : 0;
+        const int hi = j < per - 1 ? j : per - 1;
+        float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int ci = lo; ci <= hi; ++ci) {
+            const int i = ci + a.R;
+            if (i == j) continue;
+            // j is context slot j - i + R (left of the centre) or j - i - 1 + R (right of it)
+            const float cf = s_cf[ci * a.C + (j < i ? j - i + a.R : j - i - 1 + a.R)];
+            const float4 x = s_row[ci * LPR + c];
+            g.x = fmaf(cf, x.x, g.x);
+            g.y = fmaf(cf, x.y, g.y);
+            g.z = fmaf(cf, x.z, g.z);
+            g.w = fmaf(cf, x.w, g.w);
+        }
+        *reinterpret_cast<float4 *>(a.agg + (w * a.L + j) * a.d + col) = g;
+    }
+    if (blockIdx.y == 0) {
+        for (int j = threadIdx.x; j < a.L; j += 256) {
+            const int32_t id = s_pos[j];
+            const bool ok = id >= 0 && id < a.V;
+            if (!ok) dw::status_or(a.status, DW_S_BAD_INDEX);
+            const int64_t at = n_neg + w * a.L + j;
+            a.rec_key[at] = static_cast<uint32_t>(ok ? id : 0);
+            a.rec_val[at] = pack_record(ok ? 1.f : 0.f, AGG_BIT | static_cast<uint32_t>(w * a.L + j));
+        }
+    }
 }
 
 // Pass 2: records sorted by output row -> g_out[row] += sum coef * w_in[centre].
@@ -878,7 +991,7 @@ __global__ void __launch_bounds__(WAVES_PER_BLOCK *WAVE)
     k_rec_gather(const uint32_t *__restrict__ keys, const uint64_t *__restrict__ vals,
                  int64_t n_rec, const float *__restrict__ w_in, float *__restrict__ g_out,
                  int32_t d, OutAdam oa, const int64_t *__restrict__ range, int32_t gch,
-                 dw::Fixed fo, int32_t *status) {
+                 dw::Fixed fo, int32_t *status, const float *__restrict__ agg) {
     bool fx_range = false;
     uint32_t fx_tmax = 0u;   // EXACT: the largest |term|'s bits (the range test, at the end)
     const int lane = threadIdx.x & (WAVE - 1);
@@ -965,7 +1078,11 @@ __global__ void __launch_bounds__(WAVES_PER_BLOCK *WAVE)
                 const uint64_t v = in ? vals[e + u] : 0ull;
                 k[u] = in ? keys[e + u] : last;
                 coef[u] = in ? __uint_as_float(static_cast<uint32_t>(v >> 32)) : 0.f;
-                const float *src = w_in + static_cast<int64_t>(static_cast<uint32_t>(v)) * d + lane;
+                // an aggregate record (k_walk_agg; never on the owner / lazy paths, agg == NULL)
+                // reads its precomputed row of agg instead of a centre row of w_in
+                const uint32_t ci = static_cast<uint32_t>(v);
+                const float *src = ((ci & AGG_BIT) ? agg : w_in) +
+                                   static_cast<int64_t>(ci & ~AGG_BIT) * d + lane;
 #pragma unroll
                 for (int m = 0; m < VPL; ++m) x[u][m] = (in && live[m]) ? src[WAVE * m] : 0.f;
             }
@@ -1328,6 +1445,19 @@ int launch_pass1_g16(const SgnsArgs &a, hipStream_t st) {
         }
         DW_LAUNCH_CHECK("dw_sgns/g16");
         return DW_OK;
+    }
+    if constexpr (FROM_WALKS && !OWNER) {
+        if (a.coef_pos) {   // walk aggregation (plan_walks): positive coefficients, not records
+            switch (a.d / 64) {
+                case 1: hipLaunchKernelGGL((k_sgns_g16<1, true, 8, false, false, false, true>), g, bl, 0, st, a); break;
+                case 2: hipLaunchKernelGGL((k_sgns_g16<2, true, 4, false, false, false, true>), g, bl, 0, st, a); break;
+                case 4: hipLaunchKernelGGL((k_sgns_g16<4, true, 2, false, false, false, true>), g, bl, 0, st, a); break;
+                case 8: hipLaunchKernelGGL((k_sgns_g16<8, true, 1, false, false, false, true>), g, bl, 0, st, a); break;
+                default: return DW_E_UNSUPPORTED;
+            }
+            DW_LAUNCH_CHECK("dw_sgns/g16_agg");
+            return DW_OK;
+        }
     }
     switch (a.d / 64) {  // rows per chunk: CHR * F4 float4 registers per lane
         case 1: hipLaunchKernelGGL((k_sgns_g16<1, FROM_WALKS, 8, OWNER>), g, bl, 0, st, a); break;
@@ -1732,22 +1862,23 @@ template <int VPL, bool EXACT>
 void launch_gather_fx(dim3 g, dim3 bl, hipStream_t st, const uint32_t *keys,
                       const uint64_t *vals, int64_t n_rec, const float *w_in, float *g_out,
                       int32_t d, const OutAdam *oa, const int64_t *range, int32_t gch,
-                      const dw::Fixed &fo, int32_t *status) {
+                      const dw::Fixed &fo, int32_t *status, const float *agg) {
     const bool full = d == 64 * VPL;
     if (oa) {
         if (full)
             hipLaunchKernelGGL((k_rec_gather<VPL, false, true, EXACT>), g, bl, 0, st, keys, vals,
-                               n_rec, w_in, g_out, d, *oa, range, gch, fo, status);
+                               n_rec, w_in, g_out, d, *oa, range, gch, fo, status, agg);
         else
             hipLaunchKernelGGL((k_rec_gather<VPL, true, true, EXACT>), g, bl, 0, st, keys, vals,
-                               n_rec, w_in, g_out, d, *oa, range, gch, fo, status);
+                               n_rec, w_in, g_out, d, *oa, range, gch, fo, status, agg);
     } else {
         if (full)
             hipLaunchKernelGGL((k_rec_gather<VPL, false, false, EXACT>), g, bl, 0, st, keys,
-                               vals, n_rec, w_in, g_out, d, OutAdam{}, range, gch, fo, status);
+                               vals, n_rec, w_in, g_out, d, OutAdam{}, range, gch, fo, status,
+                               agg);
         else
             hipLaunchKernelGGL((k_rec_gather<VPL, true, false, EXACT>), g, bl, 0, st, keys, vals,
-                               n_rec, w_in, g_out, d, OutAdam{}, range, gch, fo, status);
+                               n_rec, w_in, g_out, d, OutAdam{}, range, gch, fo, status, agg);
     }
 }
 
@@ -1755,13 +1886,13 @@ template <int VPL>
 void launch_gather(dim3 g, dim3 bl, hipStream_t st, const uint32_t *keys, const uint64_t *vals,
                    int64_t n_rec, const float *w_in, float *g_out, int32_t d,
                    const OutAdam *oa, const int64_t *range, int32_t gch, const dw::Fixed &fo,
-                   int32_t *status) {
+                   int32_t *status, const float *agg) {
     if (fo.acc)
         launch_gather_fx<VPL, true>(g, bl, st, keys, vals, n_rec, w_in, g_out, d, oa, range, gch,
-                                    fo, status);
+                                    fo, status, agg);
     else
         launch_gather_fx<VPL, false>(g, bl, st, keys, vals, n_rec, w_in, g_out, d, oa, range,
-                                     gch, fo, status);
+                                     gch, fo, status, agg);
 }
 
 template <int VPL>
@@ -1783,7 +1914,8 @@ void launch_rest(hipStream_t st, int64_t V, int32_t d, float *g_out, const OutAd
 // sized for `share` of the records (grid-stride beyond).
 int launch_pass2(const uint32_t *keys, const uint64_t *vals, int64_t n_rec, const float *w_in,
                  float *g_out, int32_t d, const OutAdam *oa, int64_t V, hipStream_t st,
-                 const int64_t *range = nullptr, double share = 1.0, int32_t *status = nullptr) {
+                 const int64_t *range = nullptr, double share = 1.0, int32_t *status = nullptr,
+                 const float *agg = nullptr) {   // agg: the aggregate rows (k_walk_agg), or NULL
     dw::Fixed fo;   // deterministic mode: g_out's accumulator
     {
         const int rc = exact_of(g_out, V * d, &fo, nullptr, "dw_sgns pass 2");
@@ -1803,10 +1935,10 @@ int launch_pass2(const uint32_t *keys, const uint64_t *vals, int64_t n_rec, cons
     if (blocks < 1) blocks = 1;
     if (blocks > 65536) blocks = 65536;
     const dim3 g((unsigned)blocks), bl(WAVES_PER_BLOCK * WAVE);
-    if (d <= 64) launch_gather<1>(g, bl, st, keys, vals, n_rec, w_in, g_out, d, oa, range, gch, fo, status);
-    else if (d <= 128) launch_gather<2>(g, bl, st, keys, vals, n_rec, w_in, g_out, d, oa, range, gch, fo, status);
-    else if (d <= 256) launch_gather<4>(g, bl, st, keys, vals, n_rec, w_in, g_out, d, oa, range, gch, fo, status);
-    else if (d <= 512) launch_gather<8>(g, bl, st, keys, vals, n_rec, w_in, g_out, d, oa, range, gch, fo, status);
+    if (d <= 64) launch_gather<1>(g, bl, st, keys, vals, n_rec, w_in, g_out, d, oa, range, gch, fo, status, agg);
+    else if (d <= 128) launch_gather<2>(g, bl, st, keys, vals, n_rec, w_in, g_out, d, oa, range, gch, fo, status, agg);
+    else if (d <= 256) launch_gather<4>(g, bl, st, keys, vals, n_rec, w_in, g_out, d, oa, range, gch, fo, status, agg);
+    else if (d <= 512) launch_gather<8>(g, bl, st, keys, vals, n_rec, w_in, g_out, d, oa, range, gch, fo, status, agg);
     else return DW_E_UNSUPPORTED;
     DW_LAUNCH_CHECK("dw_sgns/gather");
     if (fo.acc && n_rec > 0) {   // the straddling rows' exact sums into g_out
@@ -1856,6 +1988,105 @@ struct PhaseTimer {
     }
 };
 PhaseTimer g_timer;
+
+// ---- walk aggregation: the predicate and the workspace plan of the walks forms ----------------
+// dw_sgns_set_walk_agg's mode: -1 auto, 0 off, 1 on wherever supported. Initial value from the
+// environment (DW_SGNS_WALK_AGG = 0 / 1, anything else auto), read once at load.
+int walk_agg_env() {
+    const char *e = getenv("DW_SGNS_WALK_AGG");
+    if (e && e[0] == '0' && e[1] == '\0') return 0;
+    if (e && e[0] == '1' && e[1] == '\0') return 1;
+    return -1;
+}
+std::atomic<int> g_walk_agg_mode{walk_agg_env()};
+
+constexpr size_t AGG_LDS_MAX = 64 * 1024;   // k_walk_agg's staging must fit one block's LDS
+
+inline int walk_agg_slice(int32_t d) { return d == 64 ? 64 : 128; }
+
+size_t walk_agg_lds(int32_t L, int32_t R, int32_t d) {
+    const size_t per = static_cast<size_t>(L - 2 * R);
+    return per * walk_agg_slice(d) * 4 + per * 2 * R * 4 + static_cast<size_t>(L) * 4;
+}
+
+// The shapes k_walk_agg and the AGG pass 1 take: the g16 kernels' (d in {64, 128, 256, 512},
+// 2R(1+K) <= 64), aggregate rows indexed below 2^31, and the LDS fit.
+bool walk_agg_shape_ok(int64_t n_walks, int32_t L, int32_t R, int32_t K, int32_t d) {
+    if (!(d == 64 || d == 128 || d == 256 || d == 512)) return false;
+    if (2 * (int64_t)R * (1 + (int64_t)K) > G16_TMAX) return false;
+    if (n_walks < 1 || n_walks * L >= 0x7FFFFFFF) return false;
+    return walk_agg_lds(L, R, d) <= AGG_LDS_MAX;
+}
+
+// The one predicate (with `exact`: a deterministic accumulator on g_out or g_in — its
+// fixed-point sums are per term, so that mode keeps the per-term records).
+bool walk_agg_active(int64_t n_walks, int32_t L, int32_t R, int32_t K, int32_t d, bool exact) {
+    const int mode = g_walk_agg_mode.load();
+    if (mode == 0 || exact || !walk_agg_shape_ok(n_walks, L, R, K, d)) return false;
+    // auto: only where it at least halves the positive records
+    return mode == 1 || 2 * (int64_t)R * (L - 2 * R) >= 2 * (int64_t)L;
+}
+
+bool exact_registered(const float *g) {
+    if (!g) return false;
+    std::lock_guard<std::mutex> lk(g_exact_mu);
+    return g_exact.find(g) != g_exact.end();
+}
+
+// Records and workspace of a walks call: legacy (agg false) one record per (centre, slot);
+// aggregated: the negatives' records at [0, n_neg), the aggregate records at [n_neg, n_rec),
+// then (past the legacy-shaped part for n_rec records) coef_pos and the aggregate rows.
+struct WalkPlan {
+    bool agg;
+    int64_t n_neg, n_rec;
+    Workspace ws;
+    float *coef_pos, *agg_rows;
+    size_t total;
+};
+
+int plan_walks(int64_t n_walks, int32_t L, int32_t R, int32_t K, int64_t V, int32_t d, bool agg,
+               void *base, WalkPlan *p, hipStream_t st) {
+    const int64_t batch = n_walks * (L - 2 * R), C = 2 * R;
+    p->agg = agg;
+    p->n_neg = agg ? batch * C * K : 0;
+    p->n_rec = agg ? p->n_neg + n_walks * L : batch * C * (1 + (int64_t)K);
+    DW_REQUIRE(p->n_rec < 0x7FFFFFFF, "dw_sgns: records mode needs fewer than 2^31 records");
+    const int rc = plan_workspace(p->n_rec > 0 ? p->n_rec : 1, V, base, &p->ws, st);
+    if (rc != DW_OK) return rc;
+    p->total = p->ws.total;
+    p->coef_pos = p->agg_rows = nullptr;
+    if (agg) {
+        char *b = static_cast<char *>(base);
+        p->coef_pos = reinterpret_cast<float *>(b + p->total);
+        p->total += align256(static_cast<size_t>(batch * C) * 4);
+        p->agg_rows = reinterpret_cast<float *>(b + p->total);
+        p->total += align256(static_cast<size_t>(n_walks * L) * d * 4);
+    }
+    return DW_OK;
+}
+
+// A walks call's plan from its arguments alone (phase 1, phase 2, the fused-Adam phase 2 and the
+// pieces are separate calls and must agree). The accumulators of the deterministic mode are
+// registered on both gradient buffers or on neither (a call without g_in tests g_out's).
+int plan_walks_for(const SgnsArgs &a, void *base, WalkPlan *p, hipStream_t st) {
+    const int64_t n_walks = a.batch / (a.L - 2 * a.R);
+    const bool exact = exact_registered(a.g_out) || exact_registered(a.g_in);
+    return plan_walks(n_walks, a.L, a.R, a.K, a.V, a.d,
+                      walk_agg_active(n_walks, a.L, a.R, a.K, a.d, exact), base, p, st);
+}
+
+int launch_walk_agg(const SgnsArgs &a, const WalkPlan &p, hipStream_t st) {
+    const int64_t n_walks = a.batch / (a.L - 2 * a.R);
+    const int sl = walk_agg_slice(a.d);
+    const dim3 g((unsigned)n_walks, (unsigned)(a.d / sl)), bl(256);
+    const size_t lds = walk_agg_lds(a.L, a.R, a.d);
+    if (sl == 64)
+        hipLaunchKernelGGL(k_walk_agg<64>, g, bl, lds, st, a, p.n_neg);
+    else
+        hipLaunchKernelGGL(k_walk_agg<128>, g, bl, lds, st, a, p.n_neg);
+    DW_LAUNCH_CHECK("dw_sgns/walk_agg");
+    return DW_OK;
+}
 
 // phase 0: the whole call. phase 1: pass 1 only (centre-table gradients, loss sums, records).
 // phase 2: the records sort + pass 2 (output-table gradients) of a preceding phase-1 call with
@@ -1908,22 +2139,40 @@ int launch_sgns_impl(SgnsArgs a, void *workspace, size_t workspace_bytes, int ph
     DW_REQUIRE(T <= TMAX, "dw_sgns: records mode needs 2R(1+K) <= %d (got %lld)", TMAX,
                (long long)T);
     DW_REQUIRE(a.V <= 0x7FFFFFFF, "dw_sgns: records mode needs vocab_size < 2^31");
-    const int64_t n_rec = a.batch * T;
-    DW_REQUIRE(n_rec < 0x7FFFFFFF, "dw_sgns: records mode needs batch*2R(1+K) < 2^31");
-    Workspace ws;
-    int rc = plan_workspace(n_rec, a.V, workspace, &ws, st);
+    DW_REQUIRE(a.batch * T < 0x7FFFFFFF, "dw_sgns: records mode needs batch*2R(1+K) < 2^31");
+    WalkPlan plan;
+    int rc;
+    if constexpr (FROM_WALKS) {
+        rc = plan_walks_for(a, workspace, &plan, st);
+    } else {   // pairs: one record per (centre, slot)
+        plan.agg = false;
+        plan.n_neg = 0;
+        plan.n_rec = a.batch * T;
+        plan.coef_pos = plan.agg_rows = nullptr;
+        rc = plan_workspace(plan.n_rec, a.V, workspace, &plan.ws, st);
+        plan.total = plan.ws.total;
+    }
     if (rc != DW_OK) return rc;
-    DW_REQUIRE(workspace_bytes >= ws.total, "dw_sgns: workspace too small (%zu < %zu)",
-               workspace_bytes, ws.total);
+    const Workspace &ws = plan.ws;
+    const int64_t n_rec = plan.n_rec;
+    DW_REQUIRE(workspace_bytes >= plan.total, "dw_sgns: workspace too small (%zu < %zu)%s",
+               workspace_bytes, plan.total,
+               plan.agg ? " (walk aggregation: size it with dw_sgns_walks_workspace_bytes)" : "");
     if (do1) {
         a.rec_key = ws.k0;
         a.rec_val = ws.v0;
+        a.coef_pos = plan.coef_pos;   // (NULL without aggregation)
+        a.agg = plan.agg_rows;
         int32_t fl = 0;
         rc = exact_of(a.g_in, a.V * a.d, &a.fx_in, &fl, "dw_sgns pass 1");
         if (rc != DW_OK) return rc;
         rc = launch_pass1_g16<FROM_WALKS>(a, st);
-        if (rc == DW_E_UNSUPPORTED) rc = launch_pass1<FROM_WALKS, true>(a, st);
+        if (rc == DW_E_UNSUPPORTED && !plan.agg) rc = launch_pass1<FROM_WALKS, true>(a, st);
         if (rc != DW_OK) return rc;
+        if (plan.agg) {   // inside the pass-1 window of dw_sgns_phase_ms
+            rc = launch_walk_agg(a, plan, st);
+            if (rc != DW_OK) return rc;
+        }
         if (a.fx_in.acc && !(fl & (DW_EXACT_DEFER | DW_EXACT_ADAM))) {   // the centres' exact
             int64_t cb = (a.batch + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
             if (cb > grid_cap(8)) cb = grid_cap(8);
@@ -1945,7 +2194,7 @@ int launch_sgns_impl(SgnsArgs a, void *workspace, size_t workspace_bytes, int ph
     }
     g_timer.mark(2, st);
     return launch_pass2(kb.current(), vb.current(), n_rec, a.w_in, a.g_out, a.d, oa, a.V, st,
-                        nullptr, 1.0, a.status);
+                        nullptr, 1.0, a.status, plan.agg_rows);
 }
 
 // ---- output-table phase in row pieces (N > 1: exchange a piece while the next one runs) -------
@@ -1984,13 +2233,14 @@ int launch_pieces(SgnsArgs a, void *workspace, size_t workspace_bytes, int piece
                n_pieces, (long long)piece_rows, (long long)a.V);
     const int64_t T = (int64_t)a.C * (1 + a.K);
     DW_REQUIRE(T <= TMAX && a.V <= 0x7FFFFFFF, "dw_sgns_walks_phase2_piece: records mode limits");
-    const int64_t n_rec = a.batch * T;
-    DW_REQUIRE(n_rec < 0x7FFFFFFF, "dw_sgns_walks_phase2_piece: too many records");
-    Workspace ws;
-    int rc = plan_workspace(n_rec > 0 ? n_rec : 1, a.V, workspace, &ws, st);
+    DW_REQUIRE(a.batch * T < 0x7FFFFFFF, "dw_sgns_walks_phase2_piece: too many records");
+    WalkPlan plan;   // the preceding phase-1 call's (the same arguments)
+    int rc = plan_walks_for(a, workspace, &plan, st);
     if (rc != DW_OK) return rc;
-    DW_REQUIRE(workspace_bytes >= ws.total, "dw_sgns: workspace too small (%zu < %zu)",
-               workspace_bytes, ws.total);
+    const Workspace &ws = plan.ws;
+    const int64_t n_rec = a.batch > 0 ? plan.n_rec : 0;
+    DW_REQUIRE(workspace_bytes >= plan.total, "dw_sgns: workspace too small (%zu < %zu)",
+               workspace_bytes, plan.total);
     if (piece == -1) {
         bool in_k1 = false;
         if (n_rec > 0) {
@@ -2025,7 +2275,8 @@ int launch_pieces(SgnsArgs a, void *workspace, size_t workspace_bytes, int piece
     }
     if (n_rec > 0) {
         rc = launch_pass2(in_k1 ? ws.k1 : ws.k0, in_k1 ? ws.v1 : ws.v0, n_rec, a.w_in, a.g_out,
-                          a.d, nullptr, a.V, st, ws.bounds + piece, 2.0 / n_pieces);
+                          a.d, nullptr, a.V, st, ws.bounds + piece, 2.0 / n_pieces, nullptr,
+                          plan.agg_rows);
         if (rc != DW_OK) return rc;
     }
     if (piece == n_pieces - 1) g_timer.mark(3, st);
@@ -3057,6 +3308,47 @@ int dw_sgns_workspace_bytes(int64_t n_centres, int32_t n_ctx, int32_t neg_sample
     if (rc != DW_OK) return rc;
     *bytes = ws.total;
     return DW_OK;
+}
+
+int dw_sgns_walks_workspace_bytes(int64_t n_walks, int32_t walk_length, int32_t context_radius,
+                                  int32_t neg_samples, int64_t vocab_size, int32_t dim,
+                                  size_t *bytes) {
+    DW_REQUIRE(bytes, "dw_sgns_walks_workspace_bytes: bytes is null");
+    DW_REQUIRE(n_walks >= 0 && context_radius >= 1 && walk_length >= 2 * context_radius + 1 &&
+                   neg_samples >= 0 && vocab_size >= 1 && dim >= 1,
+               "dw_sgns_walks_workspace_bytes: bad sizes");
+    const int64_t n_rec = n_walks * (walk_length - 2 * context_radius) * 2 * context_radius *
+                          (1 + (int64_t)neg_samples);
+    DW_REQUIRE(n_rec < 0x7FFFFFFF, "dw_sgns_walks_workspace_bytes: too many records");
+    WalkPlan p;
+    char dummy;
+    int rc = plan_walks(n_walks, walk_length, context_radius, neg_samples, vocab_size, dim, false,
+                        &dummy, &p, nullptr);
+    if (rc != DW_OK) return rc;
+    size_t need = p.total;
+    // whatever dw_sgns_set_walk_agg says at the calls: the larger of the two layouts
+    if (walk_agg_shape_ok(n_walks, walk_length, context_radius, neg_samples, dim)) {
+        rc = plan_walks(n_walks, walk_length, context_radius, neg_samples, vocab_size, dim, true,
+                        &dummy, &p, nullptr);
+        if (rc != DW_OK) return rc;
+        need = p.total > need ? p.total : need;
+    }
+    *bytes = need;
+    return DW_OK;
+}
+
+int dw_sgns_set_walk_agg(int32_t mode) {
+    DW_REQUIRE(mode >= -1 && mode <= 1, "dw_sgns_set_walk_agg: mode must be -1, 0 or 1");
+    g_walk_agg_mode.store(mode);
+    return DW_OK;
+}
+
+int dw_sgns_walk_agg_active(int64_t n_walks, int32_t walk_length, int32_t context_radius,
+                            int32_t neg_samples, int32_t dim) {
+    DW_REQUIRE(n_walks >= 0 && context_radius >= 1 && walk_length >= 2 * context_radius + 1 &&
+                   neg_samples >= 0 && dim >= 1,
+               "dw_sgns_walk_agg_active: bad sizes");
+    return walk_agg_active(n_walks, walk_length, context_radius, neg_samples, dim, false) ? 1 : 0;
 }
 
 namespace {

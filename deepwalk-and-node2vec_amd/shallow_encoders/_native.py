@@ -39,7 +39,7 @@ DW_EXACT_ADAM = 2
 DW_METHOD_DEEPWALK = 0
 DW_METHOD_NODE2VEC = 1
 
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 _p = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -133,6 +133,9 @@ SIGNATURES = {
     'dw_sgns_pairs': (ctypes.c_int, [_p, _p, _i64, _i32, _i32, _i64, _i32, _p, _p, _p, _p,
                                      _p, _u64, _u64, _f32, _p, _p, _p, ctypes.c_size_t, _p]),
     'dw_sgns_workspace_bytes': (ctypes.c_int, [_i64, _i32, _i32, _i64, _szp]),
+    'dw_sgns_walks_workspace_bytes': (ctypes.c_int, [_i64, _i32, _i32, _i32, _i64, _i32, _szp]),
+    'dw_sgns_set_walk_agg': (ctypes.c_int, [_i32]),
+    'dw_sgns_walk_agg_active': (ctypes.c_int, [_i64, _i32, _i32, _i32, _i32]),
     'dw_sgns_pooled_pairs': (ctypes.c_int, [_p, _i32, _p, _i64, _i32, _i32, _i64, _i32, _p, _p,
                                             _p, _p, _p, _u64, _u64, _f32, _p, _p, _p]),
     'dw_sgns_noise': (ctypes.c_int, [_i64, _i32, _i32, _i64, _u64, _u64, _p, _p]),

@@ -118,7 +118,8 @@ class GraphedStep:
         walker._next_walk_id = next_wid
         from shallow_encoders.word2vec.sgns import _use_records, workspace_for
         if scatter == 'sorted' and _use_records(scatter, 2 * R, K, tables.V):
-            workspace_for(self.centres, 2 * R, K, tables.V, dev)
+            workspace_for(self.centres, 2 * R, K, tables.V, dev, n_walks=self.B, walk_length=L,
+                          dim=int(tables.w_in.shape[1]))
         torch.cuda.synchronize(dev)
         # `unroll` consecutive steps per graph (one launch per `unroll` steps: at tiny batches
         # the gap between replays is as long as the step). One graph per parity of the in-table

@@ -49,15 +49,24 @@ def _use_records(scatter: str, n_ctx: int, neg_samples: int, vocab_size: int) ->
 
 def workspace_for(n_centres: int, n_ctx: int, neg_samples: int, vocab_size: int,
                   device: torch.device, local_rows: Optional[int] = None,
-                  slot: int = 0) -> torch.Tensor:
+                  slot: int = 0, *, n_walks: Optional[int] = None,
+                  walk_length: Optional[int] = None, dim: Optional[int] = None) -> torch.Tensor:
     """Device workspace of the atomic-free (records) output-table path, cached per device and
     grown on demand (allocated outside any timed region after the first call). ``local_rows``:
     sized for dw_sgns_owner_pass1 (records keyed by the rank's local out-table rows). ``slot``:
     a second workspace (1) for the pipelined step (owner_lazy_steps: the next batch's records
-    are placed while this one's are read)."""
+    are placed while this one's are read). ``n_walks``, ``walk_length``, ``dim`` (all three, the
+    walks forms): sized by dw_sgns_walks_workspace_bytes — with the positive coefficients and
+    the aggregate rows of the walk aggregation, whatever dw_sgns_set_walk_agg says later."""
     import ctypes
     nbytes = ctypes.c_size_t(0)
-    if local_rows is None:
+    if local_rows is None and n_walks is not None:
+        if walk_length is None or dim is None:
+            raise ValueError('workspace_for: n_walks needs walk_length and dim')
+        _native.call('dw_sgns_walks_workspace_bytes', int(n_walks), int(walk_length),
+                     int(n_ctx) // 2, int(neg_samples), int(vocab_size), int(dim),
+                     ctypes.byref(nbytes))
+    elif local_rows is None:
         _native.call('dw_sgns_workspace_bytes', int(n_centres), int(n_ctx), int(neg_samples),
                      int(vocab_size), ctypes.byref(nbytes))
     else:
@@ -119,7 +128,7 @@ def sgns_accumulate(w_in: torch.Tensor, w_out: torch.Tensor, g_in: torch.Tensor,
             if noise is not None and noise.numel() != n_centres * C * K:
                 raise ValueError('noise must have B\' * 2R * K entries')
             scale = 1.0 / max(n_centres * C, 1) if grad_scale is None else grad_scale
-            ws = workspace_for(n_centres, C, K, V, dev) \
+            ws = workspace_for(n_centres, C, K, V, dev, n_walks=n, walk_length=L, dim=d) \
                 if _use_records(scatter, C, K, V) else None
             if out_adam is not None:
                 if phase != 2 or ws is None:
@@ -193,7 +202,7 @@ def sgns_phase2_pieces(w_in: torch.Tensor, g_out: torch.Tensor, neg_samples: int
         return
     if status is None:
         status = torch.zeros(1, dtype=torch.int32, device=dev)
-    ws = workspace_for(n * (L - 2 * R), C, K, V, dev)
+    ws = workspace_for(n * (L - 2 * R), C, K, V, dev, n_walks=n, walk_length=L, dim=d)
     with torch.cuda.device(dev):
         for p in range(-1, n_pieces):
             _native.call('dw_sgns_walks_phase2_piece', p, int(n_pieces), int(piece_rows),
@@ -372,6 +381,24 @@ def renorm_(weight: torch.Tensor, ids: torch.Tensor, max_norm: float,
         _native.check_status(st, 'embedding renorm')
 
 
+def set_walk_agg(mode: int) -> None:
+    """dw_sgns_set_walk_agg: -1 auto (default), 0 off, 1 on wherever supported — the walk
+    aggregation of the walks forms' records path (A/B measurements and tests; every call of one
+    step, and a captured graph's, must see one mode)."""
+    _native.call('dw_sgns_set_walk_agg', int(mode))
+
+
+def walk_agg_active(n_walks: int, L: int, R: int, K: int, d: int) -> bool:
+    """Whether a walks call of this shape aggregates each walk position's positive out-gradient
+    terms under the current mode (dw_sgns_walk_agg_active: the library's own predicate)."""
+    if n_walks < 0 or R < 1 or L < 2 * R + 1 or K < 0 or d < 1:
+        return False
+    rc = _native.load().dw_sgns_walk_agg_active(int(n_walks), int(L), int(R), int(K), int(d))
+    if rc < 0:
+        raise _native.DWError('dw_sgns_walk_agg_active failed')
+    return rc == 1
+
+
 def sgns_phase_bytes(n_walks: int, L: int, R: int, K: int, d: int, V: int, scatter: str,
                      fused: bool = False) -> Dict[str, float]:
     """Implementation byte model of each SGNS phase per call of dw_sgns_walks: rows of 4d B,
@@ -386,6 +413,19 @@ def sgns_phase_bytes(n_walks: int, L: int, R: int, K: int, d: int, V: int, scatt
                 'sort': 0, 'pass2': 0}
     bits = max(1, math.ceil(math.log2(V)))
     touched = V * (1.0 - math.exp(-n_rec / V))   # expected distinct output rows
+    if walk_agg_active(n_walks, L, R, K, d):
+        # walk aggregation (k_walk_agg, counted with pass 1): the positives leave pass 1 as 4-B
+        # coefficients; per walk L - 2R centre rows and the coefficients are read and L aggregate
+        # rows + records written; the sort and pass 2 see the negatives' records plus one
+        # aggregate record per walk position (its 4d-B row read from the aggregate buffer)
+        C = 2 * R
+        n_agg = n_walks * L
+        n_rec = centres * C * K + n_agg
+        return {'pass1': centres * (4 * d * (1 + T) + 8 * d + 12 * C * K + 4 * C)
+                + n_walks * L * 4
+                + centres * (4 * d + 4 * C) + n_agg * (4 * d + 12) + n_walks * L * 4,
+                'sort': n_rec * (4 + 24 * math.ceil(bits / 11)),
+                'pass2': n_rec * (12 + 4 * d) + (V * d * 24 if fused else touched * 8 * d)}
     return {'pass1': centres * (4 * d * (1 + T) + 8 * d + 12 * T) + n_walks * L * 4,
             'sort': n_rec * (4 + 24 * math.ceil(bits / 11)),
             'pass2': n_rec * (12 + 4 * d) + (V * d * 24 if fused else touched * 8 * d)}

@@ -463,8 +463,9 @@ int dw_edges_inline_build(const int64_t *row_ptr, const int32_t *col, int64_t n_
  *   loss_acc: float64[4] accumulated (+=): sum positive-loss, sum negative-loss (summed over K),
  *             count(sigmoid(s)>=0.5), count(sigmoid(t)>=0.5)  (trainer.py:145-150).
  *   workspace: NULL -> output-table gradients scattered with float atomics;
- *              non-NULL (>= dw_sgns_workspace_bytes) -> atomic-free output-table path: one
- *              {row, centre, coef} record per output row, radix-sorted by row, then summed per
+ *              non-NULL (>= dw_sgns_walks_workspace_bytes) -> atomic-free output-table path: one
+ *              {row, centre, coef} record per output row — with walk aggregation (below) one
+ *              per negative and one per walk position — radix-sorted by row, then summed per
  *              row from gathered centre rows (stable order: g_out is reproducible run to run
  *              except at rows straddling two 512-record chunks). The centre-table gradient is
  *              one float-atomic row per centre in both modes. */
@@ -804,6 +805,38 @@ int dw_embedding_renorm(float *weight, int64_t vocab_size, int32_t dim, const in
  * and neg_samples negatives each over a vocabulary of vocab_size rows. */
 int dw_sgns_workspace_bytes(int64_t n_centres, int32_t n_ctx, int32_t neg_samples,
                             int64_t vocab_size, size_t *bytes);
+
+/* Walk aggregation (the walks forms on the records path: dw_sgns_walks, dw_sgns_walks_phase,
+ * dw_sgns_walks_phase2_adam, dw_sgns_walks_phase2_piece). Position j of walk w is the context of
+ * at most 2R centres, all of walk w, so its positive out-gradient terms are summed once per
+ * (walk, position) — G[w][j] = sum_i coef(i, j) w_in[walk[w][i]], ascending i, fmaf, no atomics
+ * (k_walk_agg, at the end of phase 1) — and enter the sort and the gather as ONE record in place
+ * of up to 2R. Workspace layout when active: the negatives' records dense at
+ * [0, n_centres * 2R * K), then one aggregate record per position at [.., + n_walks * L):
+ * key walk[w][j], coefficient 1, centre field 1u << 31 | (w * L + j) (an id outside [0, V): key 0,
+ * coefficient 0, DW_S_BAD_INDEX); then the positive coefficients (float[n_centres * 2R]) and
+ * the aggregate rows (float[n_walks * L, dim]). g_in, the loss sums and the Philox keys are
+ * those of the per-term records; g_out is the same sums reassociated.
+ * Active when: dim in {64, 128, 256, 512} and 2R(1+K) <= 64 (the 16-lane-group pass 1),
+ * n_walks * L < 2^31, k_walk_agg's staging ((L-2R) * min(dim,128) * 4 + (L-2R) * 2R * 4 + 4L B)
+ * fits 64 KB of LDS, no deterministic accumulator (dw_exact_register) on g_out or g_in — that
+ * mode keeps the per-term records; register both buffers or neither — and, in the auto mode,
+ * 2R(L-2R) >= 2L (it at least halves the positive records).
+ *
+ * dw_sgns_walks_workspace_bytes: what the walks forms need for this shape with aggregation on or
+ * off (>= dw_sgns_workspace_bytes of the same batch). A walks call whose workspace is too small
+ * for its layout returns DW_E_INVALID_ARG.
+ * dw_sgns_set_walk_agg: -1 auto (default; the initial mode is DW_SGNS_WALK_AGG = 0 / 1 from the
+ * environment when set), 0 off, 1 on wherever supported (only the 2R(L-2R) >= 2L test is
+ * skipped). Host state read at each call: the calls of one step must see one mode.
+ * dw_sgns_walk_agg_active: 1 when a call of this shape aggregates under the current mode (no
+ * deterministic accumulator assumed), else 0; bad sizes DW_E_INVALID_ARG. */
+int dw_sgns_walks_workspace_bytes(int64_t n_walks, int32_t walk_length, int32_t context_radius,
+                                  int32_t neg_samples, int64_t vocab_size, int32_t dim,
+                                  size_t *bytes);
+int dw_sgns_set_walk_agg(int32_t mode);
+int dw_sgns_walk_agg_active(int64_t n_walks, int32_t walk_length, int32_t context_radius,
+                            int32_t neg_samples, int32_t dim);
 
 /* Profiling aid (bench.py): enable != 0 starts (and resets) per-phase HIP-event timing of every
  * later dw_sgns_walks / dw_sgns_pairs call on this process; enable == 0 stops it.

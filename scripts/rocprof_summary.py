@@ -42,8 +42,14 @@ PROF = os.path.join(REPO, 'profiles')
 SGNS_CLASSES = ('sgns_pass1', 'sgns_sort', 'sgns_pass2')
 
 
+def rides_along(name: str) -> bool:
+    """k_walk_agg (the walk aggregation) runs once per call right after pass 1 and inside its
+    timed window: its time and bytes count as pass 1's, its dispatches are not calls."""
+    return 'k_walk_agg' in name
+
+
 def kernel_class(name: str):
-    if 'k_sgns_g16' in name or 'k_sgns<' in name or 'k_sgns(' in name:
+    if 'k_sgns_g16' in name or 'k_sgns<' in name or 'k_sgns(' in name or rides_along(name):
         return 'sgns_pass1'
     if 'k_rec_gather' in name or 'k_adam_rest' in name:   # pass 2 (+ the fused out-table Adam)
         return 'sgns_pass2'
@@ -83,7 +89,7 @@ def main():
         for r in csv.DictReader(open(stats[0])):
             k = kernel_class(r['Name'])
             if k:
-                dur[k][0] += int(r['Calls'])
+                dur[k][0] += 0 if rides_along(r['Name']) else int(r['Calls'])
                 dur[k][1] += float(r['TotalDurationNs'])
     # counter passes: one file per counter group; totals per class and dispatch counts
     tot = collections.defaultdict(lambda: collections.defaultdict(float))
@@ -96,6 +102,8 @@ def main():
                 continue
             ctr = r['Counter_Name']
             tot[k][ctr] += float(r['Counter_Value'])
+            if rides_along(r['Kernel_Name']):
+                continue
             disp[k][ctr].add((path, r.get('Dispatch_Id', r.get('Correlation_Id', ''))))
     fused = any('k_adam_rest' in r['Name'] for r in csv.DictReader(open(stats[0]))) \
         if stats else False
