@@ -71,9 +71,15 @@ __global__ void k_alias_build(const int64_t *__restrict__ row_ptr, const double 
         const int64_t n = b - a;
         if (n == 0) continue;
         double sum = 0.0;
-        for (int64_t e = a; e < b; ++e) sum += w ? w[e] : 1.0;
-        if (!(sum > 0.0)) {
-            dw::status_or(status, DW_S_ZERO_WEIGHT);
+        bool neg = false;   // a weight below zero: no probability, and floor(pl * 2^32) below
+                            // would convert a negative double to uint32 (undefined)
+        for (int64_t e = a; e < b; ++e) {
+            const double we = w ? w[e] : 1.0;
+            neg = neg || we < 0.0;
+            sum += we;
+        }
+        if (neg || !(sum > 0.0)) {
+            dw::status_or(status, neg ? DW_S_NEG_WEIGHT : DW_S_ZERO_WEIGHT);
             for (int64_t e = a; e < b; ++e) {
                 prob_thr[e] = 0xFFFFFFFFu;
                 alias[e] = static_cast<int32_t>(e - a);

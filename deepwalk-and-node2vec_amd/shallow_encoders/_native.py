@@ -33,6 +33,7 @@ DW_S_RECORDS_FULL = 32
 DW_S_DUP_NEIGHBOR = 64
 DW_S_FIXED_RANGE = 128
 DW_S_BAD_TEXT = 256
+DW_S_NEG_WEIGHT = 512
 DW_EXACT_DEFER = 1
 DW_EXACT_ADAM = 2
 
@@ -299,4 +300,6 @@ def check_status(status: torch.Tensor, what: str) -> None:
                             f'fixed-point range (|term| * 2^frac >= 2^51)')
     if s & DW_S_BAD_TEXT:
         raise ValueError(f'{what}: malformed edge-list line')
+    if s & DW_S_NEG_WEIGHT:
+        raise ValueError(f'{what}: negative weight on an edge (weights must be >= 0)')
     raise RuntimeError(f'{what}: device status {s:#x}')

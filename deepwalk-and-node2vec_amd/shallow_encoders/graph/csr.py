@@ -603,19 +603,27 @@ class CSRGraph:
         return bool(d['simple_ok'])
 
     def _build_alias(self, dev) -> None:
+        """prob_thr / alias (dw_alias_build). The tables are kept only once the status check has
+        passed: a row summing to zero (ZeroDivisionError) or a negative weight (ValueError)
+        raises here, and again at the next call, instead of leaving a table for no law."""
         d = self._dev
         n = max(self.nnz, 1)
-        d['prob_thr'] = torch.empty(n, dtype=torch.int32, device=dev)  # uint32 bit pattern
-        d['alias'] = torch.empty(n, dtype=torch.int32, device=dev)
+        prob_thr = torch.empty(n, dtype=torch.int32, device=dev)  # uint32 bit pattern
+        alias = torch.empty(n, dtype=torch.int32, device=dev)
         work_p = torch.empty(n, dtype=torch.float64, device=dev)
         work_i = torch.empty(n, dtype=torch.int32, device=dev)
         st = d['status']
         with torch.cuda.device(dev):
             _native.call('dw_alias_build', _native.ptr(d['row_ptr']), _native.ptr(d['weights']),
-                         self.vocab_size, self.nnz, _native.ptr(d['prob_thr']),
-                         _native.ptr(d['alias']), _native.ptr(work_p), _native.ptr(work_i),
-                         _native.ptr(st), _native.stream(dev))
-        _native.check_status(st, 'alias build')
+                         self.vocab_size, self.nnz, _native.ptr(prob_thr), _native.ptr(alias),
+                         _native.ptr(work_p), _native.ptr(work_i), _native.ptr(st),
+                         _native.stream(dev))
+        try:
+            _native.check_status(st, 'alias build')
+        except (ZeroDivisionError, ValueError):
+            st.zero_()   # the word is shared with the graph's other builds
+            raise
+        d['prob_thr'], d['alias'] = prob_thr, alias
 
 
 # ``weights`` stays a dataclass field (constructor, repr, equality) and reads through a property:

@@ -51,6 +51,7 @@ extern "C" {
 #define DW_S_DUP_NEIGHBOR   64   /* a CSR row lists a neighbour twice (dw_csr_check_simple)          */
 #define DW_S_FIXED_RANGE   128   /* a gradient term past the deterministic fixed-point range         */
 #define DW_S_BAD_TEXT      256   /* a line of an edge-list text is malformed (dw_edgelist_parse)     */
+#define DW_S_NEG_WEIGHT    512   /* a negative edge weight reached dw_alias_build (no table law)     */
 
 #define DW_METHOD_DEEPWALK   0   /* random_walk_generator.py:56-72 ('deepwalk' and 'dfs')          */
 #define DW_METHOD_NODE2VEC   1   /* random_walk_generator.py:75-119                                  */
@@ -166,7 +167,9 @@ int dw_adj_hash_positions(const int64_t *row_ptr, const int32_t *col, int64_t n_
 /* Per-row Vose alias tables for first-order weighted sampling (the fast-mode replacement of
  * get_node_normalized_edge_weights + random.choices, random_walk_generator.py:50-53,68).
  * prob_thr[e] = floor(P_accept * 2^32) clamped to [0, 2^32-1] with 2^32-1 meaning "always";
- * alias[e] = local index (0..deg-1) of the alias entry.
+ * alias[e] = local index (0..deg-1) of the alias entry. A row whose weights do not sum to a
+ * positive number sets DW_S_ZERO_WEIGHT, a row holding a negative weight DW_S_NEG_WEIGHT; such a
+ * row gets the identity table and the caller must not walk with the result.
  * work_prob float64[nnz], work_idx int32[nnz]: caller-provided scratch. */
 int dw_alias_build(const int64_t *row_ptr, const double *weights, int64_t n_rows, int64_t nnz,
                    uint32_t *prob_thr, int32_t *alias, double *work_prob, int32_t *work_idx,
