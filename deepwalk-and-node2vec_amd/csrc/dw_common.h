@@ -116,6 +116,26 @@ __device__ __forceinline__ double wave_sum_d(double x) {
     return x;
 }
 
+// The second kernel of a reproducible float64 reduction (dw_edge_logreg, dw_node_softmax): thread
+// t adds entry t of the n_blocks partial rows of length len in block order.
+static __global__ void __launch_bounds__(64)
+    k_logreg_finish(const double *__restrict__ partial, int64_t n_blocks, int32_t len,
+                    double *__restrict__ out) {
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= len) return;
+    double s = 0.0;
+    int64_t b = 0;
+    for (; b + 32 <= n_blocks; b += 32) {   // 32 loads in flight, added in block order
+        double v[32];
+#pragma unroll
+        for (int k = 0; k < 32; ++k) v[k] = partial[(b + k) * len + t];
+#pragma unroll
+        for (int k = 0; k < 32; ++k) s += v[k];
+    }
+    for (; b < n_blocks; ++b) s += partial[b * len + t];
+    out[t] = s;
+}
+
 // Loss terms and gradient coefficient of one output row (loss.py:14-22 + its autograd):
 //   positive row: -log(clamp(sigmoid(x), 1e-6)),  d/dx = sigmoid(x) - 1  where unclamped;
 //   negative row: -log(clamp(sigmoid(-x), 1e-6)), d/dx = 1 - sigmoid(-x) where unclamped;

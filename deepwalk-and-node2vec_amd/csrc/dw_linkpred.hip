@@ -357,24 +357,6 @@ __global__ void __launch_bounds__(256)
     }
 }
 
-__global__ void __launch_bounds__(64)
-    k_logreg_finish(const double *__restrict__ partial, int64_t n_blocks, int32_t len,
-                    double *__restrict__ out) {
-    const int t = blockIdx.x * 64 + threadIdx.x;
-    if (t >= len) return;
-    double s = 0.0;
-    int64_t b = 0;
-    for (; b + 32 <= n_blocks; b += 32) {   // 32 loads in flight, added in block order
-        double v[32];
-#pragma unroll
-        for (int k = 0; k < 32; ++k) v[k] = partial[(b + k) * len + t];
-#pragma unroll
-        for (int k = 0; k < 32; ++k) s += v[k];
-    }
-    for (; b < n_blocks; ++b) s += partial[b * len + t];
-    out[t] = s;
-}
-
 template <int VEC, int G, int C>
 void logreg_launch(int64_t blocks, hipStream_t s, const float *table, int64_t V, int32_t d,
                    int32_t op, const int64_t *pairs, const uint8_t *labels, int64_t n,
@@ -498,7 +480,7 @@ int dw_edge_logreg(const float *table, int64_t vocab_size, int32_t dim, int32_t 
 #undef DW_LR
     DW_LAUNCH_CHECK("dw_edge_logreg");
     const int32_t len = dim + 3;
-    hipLaunchKernelGGL(k_logreg_finish, dim3((unsigned)((len + 63) / 64)), dim3(64), 0, s, partial,
+    hipLaunchKernelGGL(dw::k_logreg_finish, dim3((unsigned)((len + 63) / 64)), dim3(64), 0, s, partial,
                        blocks, len, out);
     DW_LAUNCH_CHECK("dw_edge_logreg (finish)");
     return DW_OK;

@@ -40,7 +40,7 @@ DW_EXACT_ADAM = 2
 DW_METHOD_DEEPWALK = 0
 DW_METHOD_NODE2VEC = 1
 
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 _p = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -147,6 +147,9 @@ SIGNATURES = {
     'dw_edge_logreg_workspace_bytes': (ctypes.c_int, [_i64, _i32, _szp]),
     'dw_edge_logreg': (ctypes.c_int, [_p, _i64, _i32, _i32, _p, _p, _i64, _p, _p, _p,
                                       ctypes.c_size_t, _p, _p]),
+    'dw_node_softmax_workspace_bytes': (ctypes.c_int, [_i64, _i32, _i32, _szp]),
+    'dw_node_softmax': (ctypes.c_int, [_p, _i64, _i32, _p, _p, _i64, _i32, _p, _p, _p, _p,
+                                       ctypes.c_size_t, _p, _p]),
     'dw_embedding_renorm_workspace_bytes': (ctypes.c_int, [_i64, _i64, _szp]),
     'dw_embedding_renorm': (ctypes.c_int, [_p, _i64, _i32, _p, _i64, _f64, _p, ctypes.c_size_t,
                                            _p, _p]),

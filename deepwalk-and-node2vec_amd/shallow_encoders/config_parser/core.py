@@ -205,6 +205,14 @@ class GraphDownstreamNodeClassificationConfig:
     visualize: bool = True
     split_algorithm: Optional[dict] = None
     classifier_params: Optional[dict] = None
+    # 'sklearn': the reference's host path over a float64 copy of the table; 'device': the
+    # fp32 table stays in HBM (shallow_encoders/graph/nodeclf.py)
+    backend: str = 'sklearn'
+
+    def __post_init__(self):
+        if self.backend not in ('sklearn', 'device'):
+            raise ValueError(f'downstream.node_classification.backend must be "sklearn" or '
+                             f'"device", got {self.backend!r}')
 
     def instantiate_split_algorithm(self):
         """The configured split (reference: config_parser/core.py:217-232). Without one, the

@@ -8,6 +8,7 @@
 continues the SAME iteration state and, in rng='python' mode, consumes the global ``random``
 stream exactly as the same number of ``__next__`` calls would.
 """
+import logging
 import os
 from typing import Dict, Optional
 
@@ -21,6 +22,8 @@ from shallow_encoders.graph.csr import CSRGraph
 from shallow_encoders.graph.random_walk_generator import RandomWalk, random_walk_factory
 from shallow_encoders.graph.rng import shuffled_range
 from shallow_encoders.word2vec.dataloader.registry import register_dataset
+
+logger = logging.getLogger('GraphDatasets')
 
 
 class RandomWalkDataset:
@@ -280,12 +283,17 @@ class EdgeListDataset(RandomWalkDataset):
 
     ``build``: 'host' (numpy), 'device' (parsed and built in HBM) or 'auto' (device when one is
     visible); both give the same arrays. ``skip_rows`` drops header lines of a text file.
+
+    ``labels_path``: an optional node-label file (edge_list.read_node_labels; ``labels_skip_rows``
+    drops its header lines). Labelled ids that are not nodes of the graph (an edge list holds no
+    isolated node) are dropped and counted in ``n_labels_dropped``; nodes without a label stay
+    unlabelled.
     """
 
     def __init__(self, walks_per_node: int, walk_length: int, method: str = 'deepwalk',
                  path: Optional[str] = None, skip_rows: int = 0, build: str = 'auto',
-                 **kwargs):
-        from shallow_encoders.graph.edge_list import read_edge_list
+                 labels_path: Optional[str] = None, labels_skip_rows: int = 0, **kwargs):
+        from shallow_encoders.graph.edge_list import read_edge_list, read_node_labels
         if path is None:
             raise ValueError('graph_edge_list needs the edge-list file: set '
                              'datamodule.additional_parameters.path=<file>')
@@ -294,5 +302,45 @@ class EdgeListDataset(RandomWalkDataset):
         on_device = build == 'device' or (build == 'auto' and torch.cuda.is_available())
         device = (kwargs.get('device') or 'cuda') if on_device else None
         graph = read_edge_list(os.path.expanduser(path), device=device, skip_rows=skip_rows)
+        self._label_arrays = None
+        self._label_dict = None
+        self.n_labels_dropped = 0
+        if labels_path is not None:
+            ids, tokens = read_node_labels(os.path.expanduser(labels_path), labels_skip_rows)
+            node_ids = graph.itos.ids
+            pos = np.minimum(np.searchsorted(node_ids, ids), len(node_ids) - 1)
+            keep = np.flatnonzero(node_ids[pos] == ids)
+            self.n_labels_dropped = len(ids) - len(keep)
+            if self.n_labels_dropped:
+                logger.info(f'{labels_path}: dropped {self.n_labels_dropped} labelled ids that '
+                            f'are not nodes of the graph.')
+            keep = keep[np.argsort(pos[keep], kind='stable')]
+            classes = sorted({tokens[k] for k in keep})
+            rank = {c: i for i, c in enumerate(classes)}
+            self._label_arrays = (
+                (pos[keep] + 1).astype(np.int64),
+                np.asarray([rank[tokens[k]] for k in keep], dtype=np.int32), classes)
         super().__init__(graph=graph, walks_per_node=walks_per_node, walk_length=walk_length,
                          method=method, **kwargs)
+
+    @property
+    def has_labels(self) -> bool:
+        return self._label_arrays is not None
+
+    @property
+    def labels(self) -> Dict[str, str]:
+        """The reference's ``{node name: label token}`` over the labelled nodes only, built on
+        first use from the graph's names."""
+        assert self.has_labels, 'This dataset does not have any labels!'
+        if self._label_dict is None:
+            rows, y, classes = self._label_arrays
+            names = self.csr.itos
+            self._label_dict = {names[int(r)]: classes[int(c)] for r, c in zip(rows, y)}
+        return self._label_dict
+
+    def label_arrays(self):
+        """(rows int64[n], y int32[n], classes list[str]): the labelled nodes' vocabulary ids,
+        ascending and never 0, and each one's class — the rank of its token among the sorted
+        distinct tokens (the numbering ``labels_to_integers`` gives the dict form)."""
+        assert self.has_labels, 'This dataset does not have any labels!'
+        return self._label_arrays

@@ -27,6 +27,11 @@ comma}, a second such number, then the end of the line or a separator followed b
 a 19th digit, a missing second field, a non-digit where a number starts or right behind one — is
 a ``ValueError`` naming its 1-based line number. Weights in text are not parsed: weighted graphs
 come in as arrays or ``.npz``.
+
+Node labels (``read_node_labels``) come in a file of their own, one line per node under the same
+line rules: optional blanks, the node's id (1-18 digits), one or more separators, the label token
+(a run of bytes other than the separators and line ends), then the end of the line or a separator
+followed by anything. An id that appears twice is a ``ValueError`` naming its second line.
 """
 import os
 import re
@@ -333,3 +338,55 @@ def read_edge_list(path: str, device=None, skip_rows: int = 0,
         raise ValueError(f'{path}: no edges (a graph without nodes has no vocabulary and '
                          f'cannot be walked)')
     return edge_list_csr(src, dst, weights, device)
+
+
+# ---- node labels ---------------------------------------------------------------------------------
+_LABEL_LINE = re.compile(rb'([0-9]{1,18})[ \t,]+([^ \t,\r\n]+)(?:[ \t,]|\Z)')
+
+
+def read_node_labels(path: str, skip_rows: int = 0) -> Tuple[np.ndarray, List[str]]:
+    """(ids int64[m], tokens list[str]) of a node-label file, in file order: ``.npz`` (integer
+    arrays ``node`` and ``label``; the labels' decimal strings are the tokens), anything else as
+    text (module docstring). Parsed on the host: the file has one line per node, not per edge."""
+    path = os.fspath(path)
+    if skip_rows < 0:
+        raise ValueError('skip_rows must be non-negative')
+    if os.path.splitext(path)[1].lower() == '.npz':
+        with np.load(path, allow_pickle=False) as f:
+            node, label = np.asarray(f['node']), np.asarray(f['label'])
+        if node.ndim != 1 or node.shape != label.shape or node.dtype.kind not in 'iu' \
+                or label.dtype.kind not in 'iu':
+            raise ValueError(f'{path}: node and label must be 1-d integer arrays of one length')
+        ids = _host_ids(node, 'node')
+        uniq, first = np.unique(ids, return_index=True)
+        if len(uniq) != len(ids):
+            second = int(np.setdiff1d(np.arange(len(ids)), first)[0])
+            raise ValueError(f'{path}: node {int(ids[second])} is labelled twice (entry '
+                             f'{second + 1})')
+        return ids, [str(int(v)) for v in label]
+    with open(path, 'rb') as f:
+        lines = f.read().split(b'\n')
+    if lines and lines[-1] == b'':
+        lines.pop()
+    ids: List[int] = []
+    tokens: List[str] = []
+    seen = set()
+    for k, line in enumerate(lines):
+        if k < skip_rows:
+            continue
+        if line.endswith(b'\r'):
+            line = line[:-1]
+        t = line.lstrip(b' \t')
+        if not t or t[:1] in (b'#', b'%'):
+            continue
+        m = _LABEL_LINE.match(t)
+        if m is None:
+            raise ValueError(f'{path}: line {k + 1} is not a node label: '
+                             f'{line[:60].decode(errors="replace")!r}')
+        node = int(m.group(1))
+        if node in seen:
+            raise ValueError(f'{path}: line {k + 1} labels node {node} a second time')
+        seen.add(node)
+        ids.append(node)
+        tokens.append(m.group(2).decode(errors='replace'))
+    return np.asarray(ids, dtype=np.int64), tokens

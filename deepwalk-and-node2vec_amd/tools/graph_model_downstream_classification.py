@@ -17,7 +17,12 @@ Negative pairs follow the reference's law: a uniform node, then a uniform node a
 non-neighbours (itself included). sklearn's LogisticRegression with the config's
 ``classifier_params``. The model only needs the checkpoint: no GPU is used here, unless
 ``downstream.edge_classification.backend=device`` selects the device path for the edge task
-(shallow_encoders/graph/linkpred.py: the graph's CSR, so ``graph_rmat`` datasets work too).
+(shallow_encoders/graph/linkpred.py: the graph's CSR, so ``graph_rmat`` datasets work too) or
+``downstream.node_classification.backend=device`` the one for the node task
+(shallow_encoders/graph/nodeclf.py: the fp32 table stays on the GPU; embeddings only, no node
+features, no 2-D plot; macro-F1 is logged beside the accuracy).
+Only the labelled vertices are classified: a ``graph_edge_list`` dataset's label file may cover
+a part of the nodes.
 """
 import argparse
 import logging
@@ -61,9 +66,10 @@ def node_classification(embeddings: np.ndarray, itos: List[str], labels: Dict[st
                         classifier_params: Optional[dict] = None,
                         plot_path: Optional[str] = None) -> Tuple[float, float]:
     """Mean and best accuracy over ``n_experiments`` (rows of ``embeddings`` follow ``itos``,
-    row 0 = ``<unk>`` is skipped)."""
-    vertices = itos[1:]
-    X = np.asarray(embeddings, dtype=np.float64)[1:]
+    row 0 = ``<unk>`` is skipped, and so is a vertex without a label)."""
+    keep = [i for i, v in enumerate(itos[1:], start=1) if v in labels]
+    vertices = [itos[i] for i in keep]
+    X = np.asarray(embeddings, dtype=np.float64)[keep]
     if features is not None:
         X = np.concatenate([X, np.stack([features[v] for v in vertices])], axis=1)
     y = np.asarray(labels_to_integers([labels[v] for v in vertices]), dtype=np.float32)
@@ -84,6 +90,36 @@ def node_classification(embeddings: np.ndarray, itos: List[str], labels: Dict[st
     if plot_path is not None:
         plot_node_classification(X, y, best_clf, best, plot_path)
     return mean, best
+
+
+def node_classification_on_device(embeddings: np.ndarray, dataset, nc) -> Dict[str, float]:
+    """``backend: device``: the same protocol with the table and the logistic regression on the
+    GPU (shallow_encoders/graph/nodeclf.py). The labelled rows come from the dataset's
+    ``label_arrays()`` where it has one, from ``labels`` and the vocabulary otherwise."""
+    import torch
+    from shallow_encoders import _native
+    from shallow_encoders.graph import nodeclf
+    if dataset.has_features:
+        raise ValueError('downstream.node_classification.backend=device classifies the '
+                         'embeddings alone: this dataset has node features (use backend=sklearn)')
+    inner = getattr(dataset, 'dataset', dataset)
+    if hasattr(inner, 'label_arrays'):
+        rows, y, _ = inner.label_arrays()
+    else:
+        itos, labels = dataset.vocab.get_itos(), dataset.labels
+        rows = [i for i, v in enumerate(itos[1:], start=1) if v in labels]
+        y = labels_to_integers([labels[itos[i]] for i in rows])
+    y = np.asarray(y, dtype=np.float32)   # the host path's label dtype (the splits see it)
+    logger.info(f'Dataset info: {len(rows)} labelled nodes, d={embeddings.shape[1]}.')
+    dev = _native.require_device(None)
+    table = torch.from_numpy(np.ascontiguousarray(embeddings, dtype=np.float32)).to(dev)
+    mean, best, confusion = nodeclf.node_classification_device(
+        table, rows, y, nc.instantiate_split_algorithm(), nc.n_experiments,
+        classifier_params=nc.classifier_params, device=dev)
+    f1 = nodeclf.macro_f1(confusion)
+    logger.info(f'Best experiment: macro-F1 {100 * f1:.2f}% (micro-F1 = accuracy '
+                f'{100 * best:.2f}%).')
+    return {'node_accuracy': mean, 'node_best': best, 'node_macro_f1': f1}
 
 
 def plot_node_classification(X, y, clf, accuracy, path) -> None:
@@ -218,7 +254,9 @@ def main(argv=None) -> Dict[str, float]:
     Path(analysis_dir).mkdir(parents=True, exist_ok=True)
     result: Dict[str, float] = {}
     nc = cfg.downstream.node_classification
-    if nc.enable:
+    if nc.enable and nc.backend == 'device':
+        result.update(node_classification_on_device(emb, dataset, nc))
+    elif nc.enable:
         plot = os.path.join(analysis_dir, 'downstream-node-classification.jpg') \
             if nc.visualize else None
         result['node_accuracy'], result['node_best'] = node_classification(

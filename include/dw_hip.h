@@ -794,6 +794,30 @@ int dw_edge_logreg(const float *table, int64_t vocab_size, int32_t dim, int32_t 
                    double *out, void *workspace, size_t workspace_bytes, int32_t *status,
                    void *stream);
 
+/* One pass of a multinomial logistic regression over the rows table[ids[i]], no float64 copy of
+ * the features stored — what sklearn's LogisticRegression.fit / .predict compute from
+ * X = embeddings[1:] in tools/graph_model_downstream_classification.py:58-86. coef
+ * double[n_classes, dim + 1] (per class the weights, then the intercept; DEVICE memory), ids
+ * int64[n], labels int32[n]. Per sample, with x the fp32 row widened exactly to float64:
+ * z_k = w_k . x + b_k, m = max_k z_k, loss = m + log sum_k exp(z_k - m) - z_y,
+ * r_k = softmax(z)_k - [k = y]. out double[n_classes * (dim + 1) + 2]:
+ * [k * (dim + 1) + j] = sum r_k x_j for j < dim and sum r_k at j = dim, then sum loss, then the
+ * number of samples whose argmax equals y. pred int32[n] (or NULL) receives the argmax, ties to
+ * the lowest class. 1 <= dim <= 512, 2 <= n_classes <= 64, vocab_size < 2^31. Both products run
+ * on v_mfma_f64_16x16x4_f64 over tiles of 16 samples; the class columns that pad n_classes to a
+ * multiple of 16 take no part in the max or the sum, and a dim that is no multiple of 4, a table
+ * that is not 16-B aligned and a short last tile take zero-filled operands. All sums float64 and
+ * reproducible bit for bit: per-block partial rows in the workspace
+ * (>= dw_node_softmax_workspace_bytes(n, dim, n_classes)) added in block order by a second
+ * kernel, a grid that depends on (n, dim) only, no float atomics. An id outside [0, vocab_size)
+ * or a label outside [0, n_classes) sets DW_S_BAD_INDEX: that sample contributes nothing to any
+ * sum and its pred is -1 (nothing out of range is read). n = 0 writes nothing. */
+int dw_node_softmax_workspace_bytes(int64_t n, int32_t dim, int32_t n_classes, size_t *bytes);
+int dw_node_softmax(const float *table, int64_t vocab_size, int32_t dim, const int64_t *ids,
+                    const int32_t *labels, int64_t n, int32_t n_classes, const double *coef,
+                    double *out, int32_t *pred, void *workspace, size_t workspace_bytes,
+                    int32_t *status, void *stream);
+
 /* nn.Embedding(max_norm=...) lookup side effect (model.py:24-25 with max_norm set; torch
  * embedding_renorm_): every DISTINCT row among ids[0..n_ids) whose L2 norm exceeds max_norm is
  * scaled by max_norm / (norm + 1e-7), in place. Ids are deduplicated on the device (radix sort
