@@ -31,6 +31,7 @@ SOURCES = ['dw_abi.cpp', 'dw_host.cpp', 'dw_mt_host.cpp', 'dw_graph.hip', 'dw_wa
 EXTRA = {'dw_walk.hip': ['-ffp-contract=off'], 'dw_linkpred.hip': ['-ffp-contract=off'],
          'dw_sgd.hip': ['-ffp-contract=off'], 'dw_mt_host.cpp': ['-x', 'c++']}
 HEADERS = [os.path.join(HERE, 'dw_common.h'), os.path.join(HERE, 'dw_ingest.h'),
+           os.path.join(HERE, 'dw_strtod.h'),
            os.path.join(REPO, 'include', 'dw_hip.h')]
 BASE_FLAGS = ['-x', 'hip', f'--offload-arch={ARCH}', '-O3', '-fPIC', '-std=c++17',
               '-Wall', '-Wno-unused-function', '-I', os.path.join(REPO, 'include')]

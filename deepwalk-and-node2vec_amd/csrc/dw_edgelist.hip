@@ -3,6 +3,7 @@
 // for bit to CSRGraph.from_networkx(nx.Graph().add_edges_from(...)) over zero-padded names.
 //
 //   dw_edgelist_parse        text -> src, dst int64 in file order
+//   dw_edgelist_parse_weighted  "u v w" text -> src, dst, and float(w) bit for bit (float64)
 //   dw_edges_canonical       raw ids -> sorted distinct ids, unique edges packed by rank (first
 //                            occurrence kept, either orientation), their last-occurrence weights
 //   dw_csr_from_edges_loops  packed edges -> CSR; a self-loop is one entry; weights by gather
@@ -15,6 +16,7 @@
 
 #include "dw_common.h"
 #include "dw_ingest.h"
+#include "dw_strtod.h"
 
 namespace {
 
@@ -174,6 +176,90 @@ __global__ void __launch_bounds__(PARSE_BLOCK)
                 if (out < capacity) {
                     src[out] = a;
                     dst[out] = b;
+                } else {
+                    dw::status_or(status, DW_S_RECORDS_FULL);
+                }
+                ++out;
+            }
+            ++c;
+        } else if (kind == LINE_BAD && !WRITE) {
+            dw::status_or(status, DW_S_BAD_TEXT);
+            atomicMin(err_line, static_cast<unsigned long long>(this_line));
+        }
+    }
+    if (!WRITE) data_cnt[s] = c;
+}
+
+// ---- text with weights -----------------------------------------------------------------------
+// parse_line with a third field: separators and a weight token (dw_strtod.h) behind the second
+// id. tok: where the token starts; s: its digits, for the write pass to convert.
+__device__ __forceinline__ int parse_line_w(const Text &t, int64_t p, int64_t &a, int64_t &b,
+                                            int64_t &tok, dw::strtod::Scan &s) {
+    int64_t q = p;
+    while (q < t.n && is_blank(t[q])) ++q;
+    if (at_eol(t, q)) return LINE_SKIP;
+    const uint8_t c = t[q];
+    if (c == '#' || c == '%') return LINE_SKIP;
+    if (!parse_id(t, q, a)) return LINE_BAD;
+    if (at_eol(t, q) || !is_sep(t[q])) return LINE_BAD;
+    while (q < t.n && is_sep(t[q])) ++q;
+    if (at_eol(t, q)) return LINE_BAD;
+    if (!parse_id(t, q, b)) return LINE_BAD;
+    if (at_eol(t, q) || !is_sep(t[q])) return LINE_BAD;
+    while (q < t.n && is_sep(t[q])) ++q;
+    if (at_eol(t, q)) return LINE_BAD;   // no third field
+    tok = q;
+    if (!dw::strtod::scan_token(t, t.n, q, &s)) return LINE_BAD;
+    if (q - tok > dw::strtod::MAX_TOKEN) return LINE_BAD;
+    if (!at_eol(t, q) && !is_sep(t[q])) return LINE_BAD;
+    return LINE_DATA;   // (the rest of the line is ignored)
+}
+
+// k_parse for weighted lines. WRITE = false checks the grammar only; WRITE = true converts each
+// token and writes the three arrays, and hands the tokens it cannot decide to the host: 0.0 in
+// weight[] and (edge index, token offset) appended through an integer counter (counts[2]), so
+// weight[] stays a pure function of the text and the list is one up to its order.
+template <bool WRITE>
+__global__ void __launch_bounds__(PARSE_BLOCK)
+    k_parse_w(const uint8_t *__restrict__ text, int64_t n, int64_t n_seg,
+              const int64_t *__restrict__ lines_incl, const uint32_t *__restrict__ lines_cnt,
+              int64_t skip_lines, uint32_t *__restrict__ data_cnt,
+              const int64_t *__restrict__ data_incl, const uint64_t *__restrict__ pow5,
+              int64_t *__restrict__ src, int64_t *__restrict__ dst, double *__restrict__ weight,
+              int64_t capacity, int64_t *__restrict__ undecided, int64_t undecided_capacity,
+              unsigned long long *n_undecided, unsigned long long *err_line, int32_t *status) {
+    __shared__ uint32_t stage[PARSE_LDS_BYTES / 4];
+    const Text t = stage_text(text, n, stage);
+    const int64_t s = blockIdx.x * static_cast<int64_t>(PARSE_BLOCK) + threadIdx.x;
+    if (s >= n_seg) return;
+    const int64_t lo = s * PARSE_SEG;
+    const int64_t hi = lo + PARSE_SEG < n ? lo + PARSE_SEG : n;
+    int64_t line = lines_incl[s] - lines_cnt[s];
+    int64_t out = 0;
+    if (WRITE) out = data_incl[s] - data_cnt[s];
+    uint32_t c = 0;
+    for (uint64_t starts = line_starts(t, lo, hi); starts != 0; starts &= starts - 1) {
+        const int64_t p = lo + (__ffsll(static_cast<unsigned long long>(starts)) - 1);
+        const int64_t this_line = line++;
+        if (this_line < skip_lines) continue;
+        int64_t a = 0, b = 0, tok = 0;
+        dw::strtod::Scan sc{0, 0, false, false};
+        const int kind = parse_line_w(t, p, a, b, tok, sc);
+        if (kind == LINE_DATA) {
+            if (WRITE) {
+                if (out < capacity) {
+                    uint64_t bits = 0;
+                    const bool decided = dw::strtod::scan_bits(sc, pow5, &bits);
+                    src[out] = a;
+                    dst[out] = b;
+                    weight[out] = __longlong_as_double(static_cast<long long>(bits));
+                    if (!decided) {
+                        const unsigned long long slot = atomicAdd(n_undecided, 1ull);
+                        if (slot < static_cast<unsigned long long>(undecided_capacity)) {
+                            undecided[2 * slot] = out;
+                            undecided[2 * slot + 1] = tok;
+                        }
+                    }
                 } else {
                     dw::status_or(status, DW_S_RECORDS_FULL);
                 }
@@ -497,6 +583,63 @@ int dw_edgelist_parse(const uint8_t *text, int64_t n_bytes, int64_t skip_lines, 
     hipLaunchKernelGGL(k_parse_totals, dim3(1), dim3(1), 0, st, data_incl, lines_incl, n_seg,
                        counts);
     DW_LAUNCH_CHECK("dw_edgelist_parse/totals");
+    return DW_OK;
+}
+
+int dw_edgelist_parse_weighted(const uint8_t *text, int64_t n_bytes, int64_t skip_lines,
+                               const uint64_t *pow5, int64_t *src, int64_t *dst, double *weight,
+                               int64_t capacity, int64_t *undecided, int64_t undecided_capacity,
+                               int64_t *counts, int64_t *err_line, int32_t *status,
+                               void *workspace, size_t workspace_bytes, void *stream) {
+    DW_REQUIRE(n_bytes >= 0 && skip_lines >= 0 && capacity >= 0 && undecided_capacity >= 0,
+               "dw_edgelist_parse_weighted: bad sizes");
+    DW_REQUIRE(counts && err_line && status && workspace && pow5 && (n_bytes == 0 || text) &&
+                   (capacity == 0 || (src && dst && weight)) &&
+                   (undecided_capacity == 0 || undecided),
+               "dw_edgelist_parse_weighted: null pointer");
+    ParsePlan p;
+    int rc = plan_parse(n_bytes, &p);
+    if (rc != DW_OK) return rc;
+    DW_REQUIRE(workspace_bytes >= p.total,
+               "dw_edgelist_parse_weighted: workspace too small (%zu < %zu)", workspace_bytes,
+               p.total);
+    hipStream_t st = dw::as_stream(stream);
+    DW_HIP_OK(hipMemsetAsync(err_line, 0xFF, 8, st), "dw_edgelist_parse_weighted: memset");
+    DW_HIP_OK(hipMemsetAsync(counts, 0, 24, st), "dw_edgelist_parse_weighted: memset");
+    if (n_bytes == 0) return DW_OK;
+    const int64_t n_seg = (n_bytes + PARSE_SEG - 1) / PARSE_SEG;
+    DW_REQUIRE((n_seg + 255) / 256 < LIMIT_31, "dw_edgelist_parse_weighted: chunk too large");
+    char *w = static_cast<char *>(workspace);
+    uint32_t *lines_cnt = reinterpret_cast<uint32_t *>(w + p.lines_cnt);
+    int64_t *lines_incl = reinterpret_cast<int64_t *>(w + p.lines_incl);
+    uint32_t *data_cnt = reinterpret_cast<uint32_t *>(w + p.data_cnt);
+    int64_t *data_incl = reinterpret_cast<int64_t *>(w + p.data_incl);
+    unsigned long long *err = reinterpret_cast<unsigned long long *>(err_line);
+    unsigned long long *n_und = reinterpret_cast<unsigned long long *>(counts + 2);
+    const dim3 grid(grid_of(n_seg)), block(PARSE_BLOCK);
+    hipLaunchKernelGGL(k_count_lines, grid, block, 0, st, text, n_bytes, n_seg, lines_cnt);
+    DW_LAUNCH_CHECK("dw_edgelist_parse_weighted/lines");
+    size_t scan_tmp = p.total - p.scan_tmp;
+    DW_HIP_OK(rocprim::inclusive_scan(w + p.scan_tmp, scan_tmp,
+                                      static_cast<const uint32_t *>(lines_cnt), lines_incl,
+                                      static_cast<size_t>(n_seg), rocprim::plus<int64_t>(), st),
+              "dw_edgelist_parse_weighted: line scan");
+    hipLaunchKernelGGL(k_parse_w<false>, grid, block, 0, st, text, n_bytes, n_seg, lines_incl,
+                       lines_cnt, skip_lines, data_cnt, data_incl, pow5, src, dst, weight,
+                       capacity, undecided, undecided_capacity, n_und, err, status);
+    DW_LAUNCH_CHECK("dw_edgelist_parse_weighted/count");
+    scan_tmp = p.total - p.scan_tmp;
+    DW_HIP_OK(rocprim::inclusive_scan(w + p.scan_tmp, scan_tmp,
+                                      static_cast<const uint32_t *>(data_cnt), data_incl,
+                                      static_cast<size_t>(n_seg), rocprim::plus<int64_t>(), st),
+              "dw_edgelist_parse_weighted: data scan");
+    hipLaunchKernelGGL(k_parse_w<true>, grid, block, 0, st, text, n_bytes, n_seg, lines_incl,
+                       lines_cnt, skip_lines, data_cnt, data_incl, pow5, src, dst, weight,
+                       capacity, undecided, undecided_capacity, n_und, err, status);
+    DW_LAUNCH_CHECK("dw_edgelist_parse_weighted/write");
+    hipLaunchKernelGGL(k_parse_totals, dim3(1), dim3(1), 0, st, data_incl, lines_incl, n_seg,
+                       counts);
+    DW_LAUNCH_CHECK("dw_edgelist_parse_weighted/totals");
     return DW_OK;
 }
 

@@ -16,6 +16,7 @@
 #include <stdlib.h>
 
 #include "dw_common.h"
+#include "dw_strtod.h"
 
 namespace {
 
@@ -60,9 +61,123 @@ inline int bit_length(uint64_t m) {
     return k;
 }
 
+// ---- 128-bit powers of five for the weighted edge-list parser (dw_strtod.h) -------------------
+// Computed once with exact integer arithmetic (5^342 has 795 bits): for q >= 0 the top 128 bits
+// of 5^q, truncated; for q < 0, floor(2^(b + 127) / 5^-q) + 1 with b the bit length of 5^-q
+// (halved if it reaches 2^128). Both have bit 127 set.
+struct Big {
+    static constexpr int LIMBS = 16;   // 1024 bits, least significant first
+    uint64_t v[LIMBS];
+
+    int bits() const {
+        for (int i = LIMBS - 1; i >= 0; --i)
+            if (v[i]) return 64 * i + bit_length(v[i]);
+        return 0;
+    }
+    bool bit(int k) const { return k >= 0 && ((v[k >> 6] >> (k & 63)) & 1u) != 0; }
+    void times5() {
+        uint64_t carry = 0;
+        for (int i = 0; i < LIMBS; ++i) {
+            const unsigned __int128 t = static_cast<unsigned __int128>(v[i]) * 5u + carry;
+            v[i] = static_cast<uint64_t>(t);
+            carry = static_cast<uint64_t>(t >> 64);
+        }
+    }
+    void twice() {
+        for (int i = LIMBS - 1; i > 0; --i) v[i] = (v[i] << 1) | (v[i - 1] >> 63);
+        v[0] <<= 1;
+    }
+    bool at_least(const Big &o) const {
+        for (int i = LIMBS - 1; i >= 0; --i)
+            if (v[i] != o.v[i]) return v[i] > o.v[i];
+        return true;
+    }
+    void minus(const Big &o) {
+        uint64_t borrow = 0;
+        for (int i = 0; i < LIMBS; ++i) {
+            const uint64_t a = v[i], b = o.v[i];
+            v[i] = a - b - borrow;
+            borrow = (a < b || (a == b && borrow)) ? 1u : 0u;
+        }
+    }
+};
+
+struct Pow5Table {
+    uint64_t w[2 * dw::strtod::TABLE_ENTRIES];
+
+    Pow5Table() {
+        Big p = {};
+        p.v[0] = 1;
+        for (int k = 0; k <= dw::strtod::Q_MAX || k <= -dw::strtod::Q_MIN; ++k) {
+            const int b = p.bits();
+            if (k <= dw::strtod::Q_MAX) {   // bits [b - 128, b) of 5^k (zeros below bit 0)
+                uint64_t hi = 0, lo = 0;
+                for (int j = 0; j < 64; ++j) {
+                    hi = (hi << 1) | (p.bit(b - 1 - j) ? 1u : 0u);
+                    lo = (lo << 1) | (p.bit(b - 65 - j) ? 1u : 0u);
+                }
+                set(k, hi, lo);
+            }
+            if (k >= 1 && k <= -dw::strtod::Q_MIN) {   // long division of 2^(b + 127) by 5^k
+                Big r = {};
+                r.v[(b - 1) >> 6] = 1ull << ((b - 1) & 63);   // 2^(b - 1) < 5^k: no quotient bit yet
+                uint64_t hi = 0, lo = 0;
+                for (int j = 0; j < 128; ++j) {
+                    r.twice();
+                    const bool one = r.at_least(p);
+                    if (one) r.minus(p);
+                    hi = (hi << 1) | (lo >> 63);
+                    lo = (lo << 1) | (one ? 1u : 0u);
+                }
+                if (++lo == 0 && ++hi == 0) {   // reached 2^128: halve
+                    hi = 1ull << 63;
+                    lo = 0;
+                }
+                set(-k, hi, lo);
+            }
+            p.times5();
+        }
+    }
+    void set(int q, uint64_t hi, uint64_t lo) {
+        w[2 * (q - dw::strtod::Q_MIN)] = hi;
+        w[2 * (q - dw::strtod::Q_MIN) + 1] = lo;
+    }
+};
+
+const Pow5Table &pow5_table() {
+    static const Pow5Table t;
+    return t;
+}
+
+struct Bytes {
+    const uint8_t *p;
+    uint8_t operator[](int64_t i) const { return p[i]; }
+};
+
 }  // namespace
 
 extern "C" {
+
+int dw_pow5_table(uint64_t *out) {
+    DW_REQUIRE(out, "dw_pow5_table: null pointer");
+    const Pow5Table &t = pow5_table();
+    for (int i = 0; i < 2 * dw::strtod::TABLE_ENTRIES; ++i) out[i] = t.w[i];
+    return DW_OK;
+}
+
+int dw_weight_token_host(const uint8_t *token, int64_t n_bytes, int32_t *kind, uint64_t *bits) {
+    DW_REQUIRE(kind && bits && n_bytes >= 0 && (token || n_bytes == 0),
+               "dw_weight_token_host: bad arguments");
+    *kind = DW_TOKEN_BAD;
+    *bits = 0;
+    dw::strtod::Scan s;
+    int64_t p = 0;
+    if (n_bytes > dw::strtod::MAX_TOKEN || !dw::strtod::scan_token(Bytes{token}, n_bytes, p, &s) ||
+        p != n_bytes)
+        return DW_OK;
+    *kind = dw::strtod::scan_bits(s, pow5_table().w, bits) ? DW_TOKEN_DECIDED : DW_TOKEN_UNDECIDED;
+    return DW_OK;
+}
 
 int dw_host_shuffle(uint32_t *mt_state, int64_t *perm, int64_t n) {
     DW_REQUIRE(mt_state && (perm || n == 0), "dw_host_shuffle: null pointer");

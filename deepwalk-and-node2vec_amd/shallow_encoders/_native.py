@@ -40,7 +40,7 @@ DW_EXACT_ADAM = 2
 DW_METHOD_DEEPWALK = 0
 DW_METHOD_NODE2VEC = 1
 
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 _p = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -78,6 +78,10 @@ SIGNATURES = {
     'dw_edgelist_workspace_bytes': (ctypes.c_int, [_i64, _i64, _szp]),
     'dw_edgelist_parse': (ctypes.c_int, [_p, _i64, _i64, _p, _p, _i64, _p, _p, _p, _p,
                                          ctypes.c_size_t, _p]),
+    'dw_edgelist_parse_weighted': (ctypes.c_int, [_p, _i64, _i64, _p, _p, _p, _p, _i64, _p, _i64,
+                                                  _p, _p, _p, _p, ctypes.c_size_t, _p]),
+    'dw_pow5_table': (ctypes.c_int, [_p]),
+    'dw_weight_token_host': (ctypes.c_int, [_p, _i64, _p, _p]),
     'dw_edges_canonical': (ctypes.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _p, _p, _p, _p,
                                           ctypes.c_size_t, _p]),
     'dw_csr_from_edges_loops': (ctypes.c_int, [_p, _p, _i64, _i64, _p, _p, _p, _p, _p,

@@ -283,6 +283,8 @@ class EdgeListDataset(RandomWalkDataset):
 
     ``build``: 'host' (numpy), 'device' (parsed and built in HBM) or 'auto' (device when one is
     visible); both give the same arrays. ``skip_rows`` drops header lines of a text file.
+    ``weighted``: a text file's third column is the edge's weight (``float(token)``, bit for bit);
+    off, the column is ignored and the graph is unweighted.
 
     ``labels_path``: an optional node-label file (edge_list.read_node_labels; ``labels_skip_rows``
     drops its header lines). Labelled ids that are not nodes of the graph (an edge list holds no
@@ -292,7 +294,8 @@ class EdgeListDataset(RandomWalkDataset):
 
     def __init__(self, walks_per_node: int, walk_length: int, method: str = 'deepwalk',
                  path: Optional[str] = None, skip_rows: int = 0, build: str = 'auto',
-                 labels_path: Optional[str] = None, labels_skip_rows: int = 0, **kwargs):
+                 labels_path: Optional[str] = None, labels_skip_rows: int = 0,
+                 weighted: bool = False, **kwargs):
         from shallow_encoders.graph.edge_list import read_edge_list, read_node_labels
         if path is None:
             raise ValueError('graph_edge_list needs the edge-list file: set '
@@ -301,7 +304,8 @@ class EdgeListDataset(RandomWalkDataset):
             raise ValueError(f'build must be auto, host or device, got {build!r}')
         on_device = build == 'device' or (build == 'auto' and torch.cuda.is_available())
         device = (kwargs.get('device') or 'cuda') if on_device else None
-        graph = read_edge_list(os.path.expanduser(path), device=device, skip_rows=skip_rows)
+        graph = read_edge_list(os.path.expanduser(path), device=device, skip_rows=skip_rows,
+                               weighted=bool(weighted))
         self._label_arrays = None
         self._label_dict = None
         self.n_labels_dropped = 0

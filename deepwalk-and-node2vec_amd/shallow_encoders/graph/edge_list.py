@@ -25,8 +25,22 @@ unsigned decimal of 1-18 digits (leading zeros allowed), one or more separators 
 comma}, a second such number, then the end of the line or a separator followed by anything
 (extra columns are ignored, as ``nx.read_edgelist(data=False)`` does). Every other line — a sign,
 a 19th digit, a missing second field, a non-digit where a number starts or right behind one — is
-a ``ValueError`` naming its 1-based line number. Weights in text are not parsed: weighted graphs
-come in as arrays or ``.npz``.
+a ``ValueError`` naming its 1-based line number.
+
+Weighted text (``weighted=True``; off by default, and then a third column is an extra column like
+any other): a data line is the two ids as above, one or more separators, and a weight token,
+then the end of the line or a separator followed by anything. The token is an optional ``+`` or
+``-``; then digits with an optional ``.`` and more digits, or a ``.`` followed by at least one
+digit (``5``, ``5.``, ``5.25``, ``.25``); then an optional exponent: ``e`` or ``E``, an optional
+sign, one to four digits. Leading and trailing zeros are allowed, a token is at most 64 bytes,
+and ``-0`` gives -0.0. Everything else is a bad line naming its 1-based line number: no third
+field, ``nan`` / ``inf`` / ``infinity`` in any case, hex, ``_``, ``1e``, ``.``, ``e5``,
+``1.2.3``, ``--1``, ``1.5x``. The weight is ``float(token)`` bit for bit — what networkx stores
+— on both paths: the host calls ``float``; the device converts in integer arithmetic
+(Eisel-Lemire; csrc/dw_strtod.h) and hands the few tokens it cannot decide (more than 19
+significant digits that the first 19 do not settle, subnormal, underflowing or overflowing
+values) back to the host's ``float`` chunk by chunk. A token whose value rounds to +-inf
+(``1e999``) is a ``ValueError`` naming its line; underflow to a subnormal or to zero is legal.
 
 Node labels (``read_node_labels``) come in a file of their own, one line per node under the same
 line rules: optional blanks, the node's id (1-18 digits), one or more separators, the label token
@@ -190,16 +204,33 @@ def _edge_list_csr_device(src, dst, weights, device) -> CSRGraph:
 _DATA_LINE = re.compile(rb'([0-9]{1,18})[ \t,]+([0-9]{1,18})(?:[ \t,]|\Z)')
 
 
+_WEIGHT_TOKEN = rb'[+-]?(?:[0-9]+\.?[0-9]*|\.[0-9]+)(?:[eE][+-]?[0-9]{1,4})?'
+_WEIGHTED_LINE = re.compile(rb'([0-9]{1,18})[ \t,]+([0-9]{1,18})[ \t,]+(' + _WEIGHT_TOKEN
+                            + rb')(?:[ \t,]|\Z)')
+_TOKEN_AT = re.compile(rb'[^ \t,\r\n]*')
+MAX_WEIGHT_TOKEN = 64
+UNDECIDED_CAPACITY = 65536   # (edge, offset) entries a chunk may hand back before the host twin
+
+
+def _finite_weight(token: bytes, where: str, line_no: int) -> float:
+    w = float(token)
+    if w - w != 0.0:
+        raise ValueError(f'{where}: line {line_no}: the weight {token.decode()} is not finite')
+    return w
+
+
 def parse_lines_host(buf: bytes, skip_lines: int = 0, first_line: int = 1,
-                     where: str = 'edge list') -> Tuple[np.ndarray, np.ndarray, int]:
-    """(src, dst, lines seen) of a piece of text that starts at a line start; ``first_line``: the
-    1-based number of its first line (for the error message). The host twin of
-    dw_edgelist_parse."""
+                     where: str = 'edge list', weighted: bool = False):
+    """(src, dst, lines seen) — ``weighted``: (src, dst, weights, lines seen) — of a piece of
+    text that starts at a line start; ``first_line``: the 1-based number of its first line (for
+    the error message). The host twin of dw_edgelist_parse / dw_edgelist_parse_weighted."""
     lines = buf.split(b'\n')
     if lines and lines[-1] == b'':
         lines.pop()
     src: List[int] = []
     dst: List[int] = []
+    wts: List[float] = []
+    pattern = _WEIGHTED_LINE if weighted else _DATA_LINE
     for k, line in enumerate(lines):
         if k < skip_lines:
             continue
@@ -208,13 +239,51 @@ def parse_lines_host(buf: bytes, skip_lines: int = 0, first_line: int = 1,
         t = line.lstrip(b' \t')
         if not t or t[:1] in (b'#', b'%'):
             continue
-        m = _DATA_LINE.match(t)
-        if m is None:
-            raise ValueError(f'{where}: line {first_line + k} is not an edge: '
+        m = pattern.match(t)
+        if m is None or (weighted and len(m.group(3)) > MAX_WEIGHT_TOKEN):
+            raise ValueError(f'{where}: line {first_line + k} is not '
+                             f'{"a weighted edge" if weighted else "an edge"}: '
                              f'{line[:60].decode(errors="replace")!r}')
         src.append(int(m.group(1)))
         dst.append(int(m.group(2)))
-    return np.asarray(src, dtype=np.int64), np.asarray(dst, dtype=np.int64), len(lines)
+        if weighted:
+            wts.append(_finite_weight(m.group(3), where, first_line + k))
+    s, d = np.asarray(src, dtype=np.int64), np.asarray(dst, dtype=np.int64)
+    if weighted:
+        return s, d, np.asarray(wts, dtype=np.float64), len(lines)
+    return s, d, len(lines)
+
+
+_POW5 = {}   # device index -> the powers of five of dw_edgelist_parse_weighted, in HBM
+
+
+def _pow5_device(dev) -> torch.Tensor:
+    from shallow_encoders import _native
+    key = dev.index if dev.index is not None else torch.cuda.current_device()
+    if key not in _POW5:
+        table = np.empty(2 * 651, dtype=np.uint64)
+        _native.call('dw_pow5_table', table.ctypes.data)
+        _POW5[key] = torch.from_numpy(table.view(np.int64)).to(dev)
+    return _POW5[key]
+
+
+def _patch_undecided(und: np.ndarray, stage: np.ndarray, n: int, wbuf: torch.Tensor, where: str,
+                     lines_seen: int) -> Optional[Tuple[int, str]]:
+    """Converts the chunk's undecided tokens (rows (edge, offset) of ``und``; ``stage[:n]`` still
+    holds the text) with ``float`` and writes them into ``wbuf``. Returns (1-based line, message)
+    of the first one that is not finite, else None."""
+    und = und[np.argsort(und[:, 0], kind='stable')]
+    vals = np.empty(len(und), dtype=np.float64)
+    for i, off in enumerate(und[:, 1].tolist()):
+        token = _TOKEN_AT.match(stage[off:min(n, off + MAX_WEIGHT_TOKEN)].tobytes()).group(0)
+        v = float(token)
+        vals[i] = v
+        if v - v != 0.0:
+            line = lines_seen + int(np.count_nonzero(stage[:off] == 10)) + 1
+            return line, f'{where}: line {line}: the weight {token.decode()} is not finite'
+    wbuf[torch.from_numpy(und[:, 0].copy()).to(wbuf.device)] = torch.from_numpy(vals).to(
+        wbuf.device)
+    return None
 
 
 def _last_newline(view: np.ndarray, n: int) -> int:
@@ -256,11 +325,16 @@ def _text_chunks(path: str, stage: np.ndarray):
 
 
 def read_edge_arrays(path: str, device=None, skip_rows: int = 0,
-                     chunk_bytes: int = DEFAULT_CHUNK_BYTES):
-    """(src, dst) of a text edge list, in file order: numpy int64 arrays (``device=None``, parsed
-    on the host) or device tensors (parsed in HBM by dw_edgelist_parse, chunk by chunk)."""
-    if chunk_bytes < 1 or skip_rows < 0:
-        raise ValueError('chunk_bytes must be positive and skip_rows non-negative')
+                     chunk_bytes: int = DEFAULT_CHUNK_BYTES, weighted: bool = False,
+                     undecided_capacity: int = UNDECIDED_CAPACITY):
+    """(src, dst) — ``weighted``: (src, dst, weights float64) — of a text edge list, in file
+    order: numpy arrays (``device=None``, parsed on the host) or device tensors (parsed in HBM by
+    dw_edgelist_parse / dw_edgelist_parse_weighted, chunk by chunk). ``undecided_capacity``: the
+    weight tokens a chunk may hand back to the host one by one; past it the host parses the whole
+    chunk's weights (the same values, slowly)."""
+    if chunk_bytes < 1 or skip_rows < 0 or undecided_capacity < 0:
+        raise ValueError('chunk_bytes must be positive, skip_rows and undecided_capacity '
+                         'non-negative')
     # one spare byte: a file of exactly chunk_bytes is then seen to end, not cut
     size = int(min(chunk_bytes, os.path.getsize(path) + 1))
     on_device = _is_device(device)
@@ -279,14 +353,49 @@ def read_edge_arrays(path: str, device=None, skip_rows: int = 0,
             ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)
             sbuf = torch.empty(cap, dtype=torch.int64, device=dev)
             dbuf = torch.empty(cap, dtype=torch.int64, device=dev)
-            info = torch.zeros(3, dtype=torch.int64, device=dev)   # edges, lines, bad line
+            # edges, lines, [undecided tokens,] bad line
+            info = torch.zeros(4 if weighted else 3, dtype=torch.int64, device=dev)
             status = torch.zeros(1, dtype=torch.int32, device=dev)
+            if weighted:
+                wbuf = torch.empty(cap, dtype=torch.float64, device=dev)
+                ubuf = torch.empty(2 * max(undecided_capacity, 1), dtype=torch.int64, device=dev)
+                pow5 = _pow5_device(dev)
     else:
         stage = np.empty(size, dtype=np.uint8)
-    srcs, dsts, lines_seen = [], [], 0
+    srcs, dsts, wtss, lines_seen = [], [], [], 0
     for n in _text_chunks(path, stage):
         skip = max(0, skip_rows - lines_seen)
-        if on_device:
+        if on_device and weighted:
+            with torch.cuda.device(dev):
+                text[:n].copy_(stage_t[:n], non_blocking=True)
+                _native.call('dw_edgelist_parse_weighted', _native.ptr(text), n, skip,
+                             _native.ptr(pow5), _native.ptr(sbuf), _native.ptr(dbuf),
+                             _native.ptr(wbuf), cap, _native.ptr(ubuf), undecided_capacity,
+                             _native.ptr(info), _native.ptr(info[3:]), _native.ptr(status),
+                             _native.ptr(ws), ws.numel(), _native.stream(dev))
+                k, n_lines, n_und, bad = (int(x) for x in info.tolist())   # synchronises
+                # the first offence of the chunk, in file order: a bad line or an infinite weight
+                first = None
+                if int(status.item()) & _native.DW_S_BAD_TEXT:
+                    first = (lines_seen + bad + 1,
+                             f'{path}: line {lines_seen + bad + 1} is not a weighted edge')
+                w_chunk = wbuf[:k]
+                if n_und > undecided_capacity:   # the host twin raises for either offence itself
+                    w_host = parse_lines_host(stage[:n].tobytes(), skip, lines_seen + 1, path,
+                                              weighted=True)[2]
+                    w_chunk = torch.from_numpy(w_host).to(dev)
+                elif n_und:
+                    inf = _patch_undecided(ubuf[:2 * n_und].cpu().numpy().reshape(-1, 2), stage,
+                                           n, wbuf, path, lines_seen)
+                    if inf is not None and (first is None or inf[0] < first[0]):
+                        first = inf
+                if first is not None:
+                    raise ValueError(first[1])
+                _native.check_status(status, 'edge-list parse')
+                srcs.append(sbuf[:k].clone())
+                dsts.append(dbuf[:k].clone())
+                wtss.append(w_chunk.clone())
+        elif on_device:
             with torch.cuda.device(dev):
                 text[:n].copy_(stage_t[:n], non_blocking=True)
                 _native.call('dw_edgelist_parse', _native.ptr(text), n, skip, _native.ptr(sbuf),
@@ -299,6 +408,12 @@ def read_edge_arrays(path: str, device=None, skip_rows: int = 0,
                 _native.check_status(status, 'edge-list parse')
                 srcs.append(sbuf[:k].clone())
                 dsts.append(dbuf[:k].clone())
+        elif weighted:
+            s, d, w, n_lines = parse_lines_host(stage[:n].tobytes(), skip, lines_seen + 1, path,
+                                                weighted=True)
+            srcs.append(s)
+            dsts.append(d)
+            wtss.append(w)
         else:
             s, d, n_lines = parse_lines_host(stage[:n].tobytes(), skip, lines_seen + 1, path)
             srcs.append(s)
@@ -307,31 +422,43 @@ def read_edge_arrays(path: str, device=None, skip_rows: int = 0,
     if on_device:
         if not srcs:
             z = torch.empty(0, dtype=torch.int64, device=dev)
-            return z, z.clone()
-        return torch.cat(srcs), torch.cat(dsts)
-    if not srcs:
-        return np.empty(0, dtype=np.int64), np.empty(0, dtype=np.int64)
-    return np.concatenate(srcs), np.concatenate(dsts)
+            out = (z, z.clone(), torch.empty(0, dtype=torch.float64, device=dev))
+        else:
+            out = (torch.cat(srcs), torch.cat(dsts), torch.cat(wtss) if weighted else None)
+    elif not srcs:
+        out = (np.empty(0, dtype=np.int64), np.empty(0, dtype=np.int64),
+               np.empty(0, dtype=np.float64))
+    else:
+        out = (np.concatenate(srcs), np.concatenate(dsts),
+               np.concatenate(wtss) if weighted else None)
+    return out if weighted else out[:2]
 
 
 def read_edge_list(path: str, device=None, skip_rows: int = 0,
-                   chunk_bytes: int = DEFAULT_CHUNK_BYTES) -> CSRGraph:
+                   chunk_bytes: int = DEFAULT_CHUNK_BYTES, weighted: bool = False) -> CSRGraph:
     """The CSR of an edge-list file: ``.npz`` (``src``, ``dst``, optional ``weight``), ``.npy``
     (int ``[m, 2]``), anything else as text (module docstring), read in chunks of ``chunk_bytes``.
-    ``device``: build in HBM (text parsed there too) instead of with numpy — the same arrays."""
+    ``device``: build in HBM (text parsed there too) instead of with numpy — the same arrays.
+    ``weighted``: a text file's third column is the edge's weight (``.npz`` carries its own
+    ``weight`` whatever the flag says; ``.npy`` has no room for one)."""
     path = os.fspath(path)
     ext = os.path.splitext(path)[1].lower()
-    weights: Optional[np.ndarray] = None
+    weights = None
     if ext == '.npz':
         with np.load(path, allow_pickle=False) as f:
             src, dst = f['src'], f['dst']
             weights = f['weight'] if 'weight' in f.files else None
     elif ext == '.npy':
+        if weighted:
+            raise ValueError(f'{path}: an .npy edge list is an integer [m, 2] array and holds '
+                             f'no weights; use .npz with a weight array, or text')
         a = np.load(path, allow_pickle=False)
         if a.ndim != 2 or a.shape[1] != 2:
             raise ValueError(f'{path}: expected an integer array of shape [m, 2], got '
                              f'{a.shape}')
         src, dst = a[:, 0], a[:, 1]
+    elif weighted:
+        src, dst, weights = read_edge_arrays(path, device, skip_rows, chunk_bytes, weighted=True)
     else:
         src, dst = read_edge_arrays(path, device, skip_rows, chunk_bytes)
     if len(src) == 0:

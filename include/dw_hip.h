@@ -50,7 +50,7 @@ extern "C" {
 #define DW_S_RECORDS_FULL   32   /* owner-form SGNS records exceeded the workspace (not expected)    */
 #define DW_S_DUP_NEIGHBOR   64   /* a CSR row lists a neighbour twice (dw_csr_check_simple)          */
 #define DW_S_FIXED_RANGE   128   /* a gradient term past the deterministic fixed-point range         */
-#define DW_S_BAD_TEXT      256   /* a line of an edge-list text is malformed (dw_edgelist_parse)     */
+#define DW_S_BAD_TEXT      256   /* a line of an edge-list text is malformed (dw_edgelist_parse*)    */
 #define DW_S_NEG_WEIGHT    512   /* a negative edge weight reached dw_alias_build (no table law)     */
 
 #define DW_METHOD_DEEPWALK   0   /* random_walk_generator.py:56-72 ('deepwalk' and 'dfs')          */
@@ -223,6 +223,38 @@ int dw_edgelist_workspace_bytes(int64_t n_text_bytes, int64_t n_edges, size_t *b
 int dw_edgelist_parse(const uint8_t *text, int64_t n_bytes, int64_t skip_lines, int64_t *src,
                       int64_t *dst, int64_t capacity, int64_t *counts, int64_t *err_line,
                       int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+
+/* dw_edgelist_parse for "u v w" lines: behind the second id a data line needs one or more
+ * separators and a weight token, then the line's end or a separator followed by anything. The
+ * token: [+-], then digits [. digits*] or . digits+, then optionally e|E [+-] 1-4 digits; at most
+ * 64 bytes; no nan, inf, hex or '_'. Every other line (no third field included) is DW_S_BAD_TEXT.
+ * weight float64 [capacity] gets float(token) bit for bit, converted in integer arithmetic
+ * (Eisel-Lemire over pow5: device uint64 [1302], the words of dw_pow5_table), except for
+ * undecided tokens — more than 19 significant digits whose rounding the first 19 do not fix, a
+ * product whose low bits do not, a subnormal, underflowing or overflowing value: those get 0.0
+ * and an entry (edge index, byte offset of the token) in undecided (device int64
+ * [2 undecided_capacity], in no particular order; entries past the capacity are dropped but
+ * counted) for the host to convert. counts (device int64 [3]): data lines, lines seen, undecided
+ * tokens. The workspace is dw_edgelist_parse's (dw_edgelist_workspace_bytes). */
+int dw_edgelist_parse_weighted(const uint8_t *text, int64_t n_bytes, int64_t skip_lines,
+                               const uint64_t *pow5, int64_t *src, int64_t *dst, double *weight,
+                               int64_t capacity, int64_t *undecided, int64_t undecided_capacity,
+                               int64_t *counts, int64_t *err_line, int32_t *status,
+                               void *workspace, size_t workspace_bytes, void *stream);
+
+/* Host only (no device needed). The table dw_edgelist_parse_weighted reads: for q = -342 .. 308
+ * the (high, low) 64-bit words of a 128-bit approximation of 5^q with bit 127 set — q >= 0: the
+ * top 128 bits of 5^q, truncated; q < 0: floor(2^(b + 127) / 5^-q) + 1, b = bit length of 5^-q.
+ * Computed once with exact integer arithmetic. out: host uint64 [1302]. */
+int dw_pow5_table(uint64_t *out);
+
+/* Host only: the kernel's token scan and conversion on token[0, n_bytes) (a testing aid).
+ * *kind = DW_TOKEN_BAD (not a weight token), DW_TOKEN_DECIDED (*bits = the double's bits) or
+ * DW_TOKEN_UNDECIDED. */
+#define DW_TOKEN_BAD       0
+#define DW_TOKEN_DECIDED   1
+#define DW_TOKEN_UNDECIDED 2
+int dw_weight_token_host(const uint8_t *token, int64_t n_bytes, int32_t *kind, uint64_t *bits);
 
 /* Raw edges (src, dst int64 [n_edges], ids in [0, 2^id_bits), id_bits <= 60: others set
  * DW_S_BAD_INDEX; weights float64 [n_edges] or NULL) to their canonical form: node_ids int64

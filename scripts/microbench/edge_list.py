@@ -7,10 +7,14 @@ per edge, into a temporary directory.
            dw_csr_from_edges_loops each between device events (warm-up, best of REPS), the parse
            against dw_stream_copy over the same bytes; and read_edge_list(device=...) end to end;
   host     the same file through the numpy / Python host path (parse and build, wall clock);
+  weighted the same edges with a third column repr(uniform + 0.5), the whole text resident in HBM:
+           dw_edgelist_parse_weighted against dw_edgelist_parse (the id-only parser) over the
+           same lines without the column, in the same call; the undecided tokens; and
+           read_edge_list(device=..., weighted=True) end to end (host patch included);
   parent   at R-MAT 16 only, the route a user had before: pandas.read_csv ->
            nx.from_pandas_edgelist -> CSRGraph.from_networkx, beside both new paths on that file.
 
-    python scripts/microbench/edge_list.py [--part device|host|parent|all] [--json PATH]
+    python scripts/microbench/edge_list.py [--part device|host|weighted|parent|all] [--json PATH]
 
 One JSON line per part on stdout (and appended to --json).
 """
@@ -135,6 +139,58 @@ def part_device(path, n_bytes, m_raw, dev, out):
           'read_edge_list_device_ms': total_ms, 'reps': REPS}, out)
 
 
+def _resident(path, dev):
+    """The whole file in HBM (one chunk, whatever its size)."""
+    return torch.from_numpy(np.fromfile(path, dtype=np.uint8)).to(dev)
+
+
+def part_weighted(edges, plain_path, plain_bytes, tmp, dev, out):
+    import pandas as pd
+    m_raw = len(edges)
+    path = os.path.join(tmp, 'weighted.txt')
+    w = np.random.default_rng(0).random(m_raw) + 0.5
+    pd.DataFrame({'u': edges[:, 0], 'v': edges[:, 1], 'w': w}).to_csv(
+        path, sep=' ', header=False, index=False)
+    n_bytes = os.path.getsize(path)
+    s = _native.stream(dev)
+    nb = ctypes.c_size_t(0)
+    _native.call('dw_edgelist_workspace_bytes', n_bytes, 0, ctypes.byref(nb))
+    ws = torch.empty(int(nb.value), dtype=torch.uint8, device=dev)
+    cap = m_raw + 1
+    src = torch.empty(cap, dtype=torch.int64, device=dev)
+    dst = torch.empty(cap, dtype=torch.int64, device=dev)
+    wt = torch.empty(cap, dtype=torch.float64, device=dev)
+    und = torch.empty(2 * el.UNDECIDED_CAPACITY, dtype=torch.int64, device=dev)
+    info = torch.zeros(4, dtype=torch.int64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    pow5 = el._pow5_device(dev)
+    text = _resident(path, dev)
+    weighted_ms = best_event_ms(lambda: _native.call(
+        'dw_edgelist_parse_weighted', _native.ptr(text), n_bytes, 0, _native.ptr(pow5),
+        _native.ptr(src), _native.ptr(dst), _native.ptr(wt), cap, _native.ptr(und),
+        el.UNDECIDED_CAPACITY, _native.ptr(info), _native.ptr(info[3:]), _native.ptr(status),
+        _native.ptr(ws), ws.numel(), s), dev)
+    m, _, n_und, _ = info.tolist()
+    assert m == m_raw and int(status.item()) == 0
+    exact = bool(np.array_equal(wt[:m].cpu().numpy().view(np.uint64), w.view(np.uint64)))
+    del text
+    text = _resident(plain_path, dev)
+    id_only_ms = best_event_ms(lambda: _native.call(
+        'dw_edgelist_parse', _native.ptr(text), plain_bytes, 0, _native.ptr(src),
+        _native.ptr(dst), cap, _native.ptr(info), _native.ptr(info[2:]), _native.ptr(status),
+        _native.ptr(ws), ws.numel(), s), dev)
+    assert int(info[0]) == m_raw and int(status.item()) == 0
+    del text, ws, src, dst, wt, und
+    total_ms = best_wall_ms(lambda: el.read_edge_list(path, device=dev, weighted=True), dev)
+    emit({'part': 'weighted', 'lines': m_raw, 'weighted_file_bytes': n_bytes,
+          'id_only_file_bytes': plain_bytes, 'weighted_parse_ms': weighted_ms,
+          'weighted_parse_gbps': n_bytes / weighted_ms / 1e6, 'id_only_parse_ms': id_only_ms,
+          'id_only_parse_gbps': plain_bytes / id_only_ms / 1e6,
+          'time_ratio': weighted_ms / id_only_ms, 'bytes_ratio': n_bytes / plain_bytes,
+          'undecided_tokens': n_und, 'weights_equal_float_before_patch': exact,
+          'read_edge_list_device_weighted_ms': total_ms, 'reps': REPS}, out)
+
+
 def part_host(path, n_bytes, m_raw, out):
     t0 = time.perf_counter()
     src, dst = el.read_edge_arrays(path)
@@ -170,19 +226,21 @@ def part_parent(tmp, dev, out):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__)
-    ap.add_argument('--part', default='all', choices=['device', 'host', 'parent', 'all'])
+    ap.add_argument('--part', default='all', choices=['device', 'host', 'weighted', 'parent', 'all'])
     ap.add_argument('--json', default=None)
     ap.add_argument('--scale', type=int, default=20)
     ap.add_argument('--draws', type=int, default=10_000_000)
     args = ap.parse_args()
     dev = _native.require_device(None)   # no device: an error, not a CPU timing
     with tempfile.TemporaryDirectory() as tmp:
-        if args.part in ('device', 'host', 'all'):
+        if args.part in ('device', 'host', 'weighted', 'all'):
             edges, _ = rmat_edges(args.scale, args.draws, seed=0)
             path = os.path.join(tmp, f'rmat{args.scale}.txt')
             n_bytes = write_text(edges, path)
             if args.part in ('device', 'all'):
                 part_device(path, n_bytes, len(edges), dev, args.json)
+            if args.part in ('weighted', 'all'):
+                part_weighted(edges, path, n_bytes, tmp, dev, args.json)
             if args.part in ('host', 'all'):
                 part_host(path, n_bytes, len(edges), args.json)
         if args.part in ('parent', 'all'):
