@@ -8,6 +8,10 @@
 //                            occurrence kept, either orientation), their last-occurrence weights
 //   dw_csr_from_edges_loops  packed edges -> CSR; a self-loop is one entry; weights by gather
 //
+// The two text entry points are one parser: parse_line<WEIGHTED> is the line grammar, k_parse<
+// WEIGHTED, WRITE> the kernel and parse_text<WEIGHTED> the launcher; the id-only instantiations
+// hold nothing of the weight token's scan and take none of its arguments.
+//
 // Every output is a pure function of the input: integer atomics only (degree counts, the
 // smallest offending line), stable radix sorts, scans and selects — reruns are bit-identical.
 #include <rocprim/device/device_radix_sort.hpp>
@@ -20,9 +24,11 @@
 
 namespace {
 
-using dw::ingest::a256;
+using dw::ingest::Arena;
 using dw::ingest::bits_for;
 using dw::ingest::grid_of;
+using dw::ingest::k_degree;
+using dw::ingest::k_row_ptr_head;
 
 // ---- text ------------------------------------------------------------------------------------
 // One lane owns PARSE_SEG consecutive bytes and parses every line that STARTS in them (reading
@@ -106,7 +112,19 @@ __device__ __forceinline__ bool parse_id(const Text &t, int64_t &q, int64_t &val
 
 enum { LINE_SKIP = 0, LINE_DATA = 1, LINE_BAD = 2 };
 
-__device__ __forceinline__ int parse_line(const Text &t, int64_t p, int64_t &a, int64_t &b) {
+// A line's weight token (dw_strtod.h): where it starts, and its digits for the write pass to
+// convert.
+struct WeightToken {
+    int64_t at;
+    dw::strtod::Scan scan;
+};
+
+// The line grammar: blanks, a comment or the first id, separators, the second id; WEIGHTED:
+// separators and a weight token of at most MAX_TOKEN bytes behind it (into w, untouched
+// otherwise); then the line's end or a separator.
+template <bool WEIGHTED>
+__device__ __forceinline__ int parse_line(const Text &t, int64_t p, int64_t &a, int64_t &b,
+                                          WeightToken &w) {
     int64_t q = p;
     while (q < t.n && is_blank(t[q])) ++q;
     if (at_eol(t, q)) return LINE_SKIP;
@@ -117,6 +135,14 @@ __device__ __forceinline__ int parse_line(const Text &t, int64_t p, int64_t &a, 
     while (q < t.n && is_sep(t[q])) ++q;
     if (at_eol(t, q)) return LINE_BAD;
     if (!parse_id(t, q, b)) return LINE_BAD;
+    if constexpr (WEIGHTED) {
+        if (at_eol(t, q) || !is_sep(t[q])) return LINE_BAD;
+        while (q < t.n && is_sep(t[q])) ++q;
+        if (at_eol(t, q)) return LINE_BAD;   // no third field
+        w.at = q;
+        if (!dw::strtod::scan_token(t, t.n, q, &w.scan)) return LINE_BAD;
+        if (q - w.at > dw::strtod::MAX_TOKEN) return LINE_BAD;
+    }
     if (!at_eol(t, q) && !is_sep(t[q])) return LINE_BAD;
     return LINE_DATA;   // (the rest of the line is ignored)
 }
@@ -146,15 +172,40 @@ __global__ void __launch_bounds__(PARSE_BLOCK)
     cnt[s] = static_cast<uint32_t>(__popcll(line_starts(t, lo, hi)));
 }
 
-// WRITE = false: data lines per segment, and the smallest bad line. WRITE = true: the edges.
-template <bool WRITE>
+// Where the edges go. The weighted parser's extra arguments live in its own bundle, so the
+// id-only kernels take (and keep in registers) nothing of them.
+template <bool WEIGHTED>
+struct ParseOut;
+
+template <>
+struct ParseOut<false> {
+    int64_t *__restrict__ src, *__restrict__ dst;
+    int64_t capacity;
+};
+
+template <>
+struct ParseOut<true> {
+    const uint64_t *__restrict__ pow5;   // dw_pow5_table, in HBM
+    int64_t *__restrict__ src, *__restrict__ dst;
+    double *__restrict__ weight;
+    int64_t capacity;
+    int64_t *__restrict__ undecided;     // (edge index, token offset) pairs
+    int64_t undecided_capacity;
+    unsigned long long *n_undecided;
+};
+
+// WRITE = false: data lines per segment, and the smallest bad line (WEIGHTED: the token's
+// grammar is checked, nothing converted). WRITE = true: the edges; WEIGHTED: each token is
+// converted too, and the tokens the conversion cannot decide go to the host: 0.0 in weight[] and
+// (edge index, token offset) appended through an integer counter (counts[2]), so weight[] stays
+// a pure function of the text and the list is one up to its order.
+template <bool WEIGHTED, bool WRITE>
 __global__ void __launch_bounds__(PARSE_BLOCK)
     k_parse(const uint8_t *__restrict__ text, int64_t n, int64_t n_seg,
             const int64_t *__restrict__ lines_incl, const uint32_t *__restrict__ lines_cnt,
             int64_t skip_lines, uint32_t *__restrict__ data_cnt,
-            const int64_t *__restrict__ data_incl, int64_t *__restrict__ src,
-            int64_t *__restrict__ dst, int64_t capacity, unsigned long long *err_line,
-            int32_t *status) {
+            const int64_t *__restrict__ data_incl, ParseOut<WEIGHTED> o,
+            unsigned long long *err_line, int32_t *status) {
     __shared__ uint32_t stage[PARSE_LDS_BYTES / 4];
     const Text t = stage_text(text, n, stage);
     const int64_t s = blockIdx.x * static_cast<int64_t>(PARSE_BLOCK) + threadIdx.x;
@@ -170,94 +221,24 @@ __global__ void __launch_bounds__(PARSE_BLOCK)
         const int64_t this_line = line++;
         if (this_line < skip_lines) continue;
         int64_t a = 0, b = 0;
-        const int kind = parse_line(t, p, a, b);
+        WeightToken w{0, {0, 0, false, false}};
+        const int kind = parse_line<WEIGHTED>(t, p, a, b, w);
         if (kind == LINE_DATA) {
             if (WRITE) {
-                if (out < capacity) {
-                    src[out] = a;
-                    dst[out] = b;
-                } else {
-                    dw::status_or(status, DW_S_RECORDS_FULL);
-                }
-                ++out;
-            }
-            ++c;
-        } else if (kind == LINE_BAD && !WRITE) {
-            dw::status_or(status, DW_S_BAD_TEXT);
-            atomicMin(err_line, static_cast<unsigned long long>(this_line));
-        }
-    }
-    if (!WRITE) data_cnt[s] = c;
-}
-
-// ---- text with weights -----------------------------------------------------------------------
-// parse_line with a third field: separators and a weight token (dw_strtod.h) behind the second
-// id. tok: where the token starts; s: its digits, for the write pass to convert.
-__device__ __forceinline__ int parse_line_w(const Text &t, int64_t p, int64_t &a, int64_t &b,
-                                            int64_t &tok, dw::strtod::Scan &s) {
-    int64_t q = p;
-    while (q < t.n && is_blank(t[q])) ++q;
-    if (at_eol(t, q)) return LINE_SKIP;
-    const uint8_t c = t[q];
-    if (c == '#' || c == '%') return LINE_SKIP;
-    if (!parse_id(t, q, a)) return LINE_BAD;
-    if (at_eol(t, q) || !is_sep(t[q])) return LINE_BAD;
-    while (q < t.n && is_sep(t[q])) ++q;
-    if (at_eol(t, q)) return LINE_BAD;
-    if (!parse_id(t, q, b)) return LINE_BAD;
-    if (at_eol(t, q) || !is_sep(t[q])) return LINE_BAD;
-    while (q < t.n && is_sep(t[q])) ++q;
-    if (at_eol(t, q)) return LINE_BAD;   // no third field
-    tok = q;
-    if (!dw::strtod::scan_token(t, t.n, q, &s)) return LINE_BAD;
-    if (q - tok > dw::strtod::MAX_TOKEN) return LINE_BAD;
-    if (!at_eol(t, q) && !is_sep(t[q])) return LINE_BAD;
-    return LINE_DATA;   // (the rest of the line is ignored)
-}
-
-// k_parse for weighted lines. WRITE = false checks the grammar only; WRITE = true converts each
-// token and writes the three arrays, and hands the tokens it cannot decide to the host: 0.0 in
-// weight[] and (edge index, token offset) appended through an integer counter (counts[2]), so
-// weight[] stays a pure function of the text and the list is one up to its order.
-template <bool WRITE>
-__global__ void __launch_bounds__(PARSE_BLOCK)
-    k_parse_w(const uint8_t *__restrict__ text, int64_t n, int64_t n_seg,
-              const int64_t *__restrict__ lines_incl, const uint32_t *__restrict__ lines_cnt,
-              int64_t skip_lines, uint32_t *__restrict__ data_cnt,
-              const int64_t *__restrict__ data_incl, const uint64_t *__restrict__ pow5,
-              int64_t *__restrict__ src, int64_t *__restrict__ dst, double *__restrict__ weight,
-              int64_t capacity, int64_t *__restrict__ undecided, int64_t undecided_capacity,
-              unsigned long long *n_undecided, unsigned long long *err_line, int32_t *status) {
-    __shared__ uint32_t stage[PARSE_LDS_BYTES / 4];
-    const Text t = stage_text(text, n, stage);
-    const int64_t s = blockIdx.x * static_cast<int64_t>(PARSE_BLOCK) + threadIdx.x;
-    if (s >= n_seg) return;
-    const int64_t lo = s * PARSE_SEG;
-    const int64_t hi = lo + PARSE_SEG < n ? lo + PARSE_SEG : n;
-    int64_t line = lines_incl[s] - lines_cnt[s];
-    int64_t out = 0;
-    if (WRITE) out = data_incl[s] - data_cnt[s];
-    uint32_t c = 0;
-    for (uint64_t starts = line_starts(t, lo, hi); starts != 0; starts &= starts - 1) {
-        const int64_t p = lo + (__ffsll(static_cast<unsigned long long>(starts)) - 1);
-        const int64_t this_line = line++;
-        if (this_line < skip_lines) continue;
-        int64_t a = 0, b = 0, tok = 0;
-        dw::strtod::Scan sc{0, 0, false, false};
-        const int kind = parse_line_w(t, p, a, b, tok, sc);
-        if (kind == LINE_DATA) {
-            if (WRITE) {
-                if (out < capacity) {
+                if (out < o.capacity) {
                     uint64_t bits = 0;
-                    const bool decided = dw::strtod::scan_bits(sc, pow5, &bits);
-                    src[out] = a;
-                    dst[out] = b;
-                    weight[out] = __longlong_as_double(static_cast<long long>(bits));
-                    if (!decided) {
-                        const unsigned long long slot = atomicAdd(n_undecided, 1ull);
-                        if (slot < static_cast<unsigned long long>(undecided_capacity)) {
-                            undecided[2 * slot] = out;
-                            undecided[2 * slot + 1] = tok;
+                    bool decided = true;
+                    if constexpr (WEIGHTED) decided = dw::strtod::scan_bits(w.scan, o.pow5, &bits);
+                    o.src[out] = a;
+                    o.dst[out] = b;
+                    if constexpr (WEIGHTED) {
+                        o.weight[out] = __longlong_as_double(static_cast<long long>(bits));
+                        if (!decided) {
+                            const unsigned long long slot = atomicAdd(o.n_undecided, 1ull);
+                            if (slot < static_cast<unsigned long long>(o.undecided_capacity)) {
+                                o.undecided[2 * slot] = out;
+                                o.undecided[2 * slot + 1] = w.at;
+                            }
                         }
                     }
                 } else {
@@ -350,21 +331,6 @@ __global__ void __launch_bounds__(256)
 }
 
 // ---- CSR with self-loops and weights -------------------------------------------------------------
-__global__ void __launch_bounds__(256)
-    k_degree_loops(const uint64_t *__restrict__ edges, int64_t m, int64_t n_nodes,
-                   uint32_t *__restrict__ deg, int32_t *status) {
-    const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
-    if (i >= m) return;
-    const uint64_t e = edges[i];
-    const uint64_t u = e >> 32, v = e & 0xFFFFFFFFull;
-    if (u >= static_cast<uint64_t>(n_nodes) || v >= static_cast<uint64_t>(n_nodes)) {
-        dw::status_or(status, DW_S_BAD_CSR);
-        return;
-    }
-    atomicAdd(deg + u, 1u);
-    if (u != v) atomicAdd(deg + v, 1u);
-}
-
 // Entry 2i = (u -> v), entry 2i+1 = (v -> u); a self-loop's second entry (and a bad edge) gets
 // the key n_nodes, which sorts past every row and is never gathered.
 __global__ void __launch_bounds__(256)
@@ -395,42 +361,46 @@ __global__ void __launch_bounds__(256)
     if (w_col) w_col[j] = weights[en >> 1];
 }
 
-__global__ void k_row_ptr_head2(int64_t *row_ptr) {
-    row_ptr[0] = 0;
-    row_ptr[1] = 0;
-}
-
 // ---- workspace plans (one size serves the three calls) ------------------------------------------
-struct ParsePlan {
-    size_t lines_cnt, lines_incl, data_cnt, data_incl, scan_tmp, total;
+struct ParseBufs {
+    uint32_t *lines_cnt;
+    int64_t *lines_incl;
+    uint32_t *data_cnt;
+    int64_t *data_incl;
+    char *scan_tmp;
+    size_t scan_tmp_bytes;
 };
 
-int plan_parse(int64_t n_bytes, ParsePlan *p) {
+int plan_parse(Arena &a, int64_t n_bytes, ParseBufs *p) {
     const int64_t n_seg = (n_bytes + PARSE_SEG - 1) / PARSE_SEG > 0
                               ? (n_bytes + PARSE_SEG - 1) / PARSE_SEG : 1;
-    size_t scan_tmp = 0;
-    DW_HIP_OK(rocprim::inclusive_scan(nullptr, scan_tmp, static_cast<const uint32_t *>(nullptr),
+    DW_HIP_OK(rocprim::inclusive_scan(nullptr, p->scan_tmp_bytes,
+                                      static_cast<const uint32_t *>(nullptr),
                                       static_cast<int64_t *>(nullptr),
                                       static_cast<size_t>(n_seg), rocprim::plus<int64_t>()),
               "dw_edgelist_parse: scan size query");
-    size_t off = 0;
-    p->lines_cnt = off;  off += a256(n_seg * 4);
-    p->lines_incl = off; off += a256(n_seg * 8);
-    p->data_cnt = off;   off += a256(n_seg * 4);
-    p->data_incl = off;  off += a256(n_seg * 8);
-    p->scan_tmp = off;   off += a256(scan_tmp);
-    p->total = off;
+    p->lines_cnt = a.take<uint32_t>(n_seg);
+    p->lines_incl = a.take<int64_t>(n_seg);
+    p->data_cnt = a.take<uint32_t>(n_seg);
+    p->data_incl = a.take<int64_t>(n_seg);
+    p->scan_tmp = a.take<char>(p->scan_tmp_bytes);
     return DW_OK;
 }
 
-struct CanonPlan {
-    size_t keys0, keys1, pos0, pos1, head, head_incl, rank_of, packed, keep, w_first, head_pos,
-        head_pos_incl, tmp, total;
+struct CanonBufs {
+    uint64_t *keys0, *keys1;
+    uint32_t *pos0, *pos1, *head, *head_incl, *rank_of;
+    uint64_t *packed;
+    uint8_t *keep;
+    double *w_first;
+    uint32_t *head_pos, *head_pos_incl;
+    int64_t *w_count;   // the weight select's count
+    char *tmp;
     size_t tmp_bytes;
     int rank_bits;   // bits of a rank: n <= 2 m, so the edge sort reads 2 * rank_bits key bits
 };
 
-int plan_canon(int64_t m, CanonPlan *p) {
+int plan_canon(Arena &a, int64_t m, CanonBufs *p) {
     const size_t n2 = 2 * static_cast<size_t>(m);
     p->rank_bits = bits_for(2 * m);
     size_t s1 = 0, s2 = 0, s3 = 0, s4 = 0, s5 = 0, s6 = 0;
@@ -462,30 +432,30 @@ int plan_canon(int64_t m, CanonPlan *p) {
     size_t tmp = s1;
     for (size_t s : {s2, s3, s4, s5, s6}) tmp = s > tmp ? s : tmp;
     p->tmp_bytes = tmp;
-    size_t off = 0;
-    p->keys0 = off;         off += a256(n2 * 8);
-    p->keys1 = off;         off += a256(n2 * 8);
-    p->pos0 = off;          off += a256(n2 * 4);
-    p->pos1 = off;          off += a256(n2 * 4);
-    p->head = off;          off += a256(n2 * 4);
-    p->head_incl = off;     off += a256(n2 * 4);
-    p->rank_of = off;       off += a256(n2 * 4);
-    p->packed = off;        off += a256(m * 8);
-    p->keep = off;          off += a256(m);
-    p->w_first = off;       off += a256(m * 8);
-    p->head_pos = off;      off += a256(m * 4);
-    p->head_pos_incl = off; off += a256(m * 4 + 8);   // + the weight select's count
-    p->tmp = off;           off += a256(tmp);
-    p->total = off;
+    p->keys0 = a.take<uint64_t>(n2);
+    p->keys1 = a.take<uint64_t>(n2);
+    p->pos0 = a.take<uint32_t>(n2);
+    p->pos1 = a.take<uint32_t>(n2);
+    p->head = a.take<uint32_t>(n2);
+    p->head_incl = a.take<uint32_t>(n2);
+    p->rank_of = a.take<uint32_t>(n2);
+    p->packed = a.take<uint64_t>(m);
+    p->keep = a.take<uint8_t>(m);
+    p->w_first = a.take<double>(m);
+    p->head_pos = a.take<uint32_t>(m);
+    p->head_pos_incl = a.take<uint32_t>(m + 2);   // + 8 bytes: the weight select's count
+    p->w_count = a.last<int64_t>();
+    p->tmp = a.take<char>(tmp);
     return DW_OK;
 }
 
-struct LoopCsrPlan {
-    size_t keys0, keys1, vals0, vals1, deg, tmp, total;
+struct LoopCsrBufs {
+    uint32_t *keys0, *keys1, *vals0, *vals1, *deg;
+    char *tmp;
     size_t tmp_bytes;
 };
 
-int plan_loop_csr(int64_t m, int64_t n_nodes, LoopCsrPlan *p) {
+int plan_loop_csr(Arena &a, int64_t m, int64_t n_nodes, LoopCsrBufs *p) {
     const size_t n2 = 2 * static_cast<size_t>(m);
     size_t s1 = 0, s2 = 0;
     rocprim::double_buffer<uint32_t> kb(nullptr, nullptr), vb(nullptr, nullptr);
@@ -496,18 +466,62 @@ int plan_loop_csr(int64_t m, int64_t n_nodes, LoopCsrPlan *p) {
                                       static_cast<size_t>(n_nodes), rocprim::plus<int64_t>()),
               "dw_csr_from_edges_loops: scan size query");
     p->tmp_bytes = s1 > s2 ? s1 : s2;
-    size_t off = 0;
-    p->keys0 = off; off += a256(n2 * 4);
-    p->keys1 = off; off += a256(n2 * 4);
-    p->vals0 = off; off += a256(n2 * 4);
-    p->vals1 = off; off += a256(n2 * 4);
-    p->deg = off;   off += a256(n_nodes * 4);
-    p->tmp = off;   off += a256(p->tmp_bytes);
-    p->total = off;
+    p->keys0 = a.take<uint32_t>(n2);
+    p->keys1 = a.take<uint32_t>(n2);
+    p->vals0 = a.take<uint32_t>(n2);
+    p->vals1 = a.take<uint32_t>(n2);
+    p->deg = a.take<uint32_t>(n_nodes);
+    p->tmp = a.take<char>(p->tmp_bytes);
     return DW_OK;
 }
 
 constexpr int64_t LIMIT_31 = int64_t(1) << 31;
+
+// The launcher of both text entry points: plan, count lines, scan, count data lines, scan,
+// write, totals. counts: edges, lines, WEIGHTED: and the undecided tokens (o.n_undecided).
+#define PARSE_MSG(tail) (WEIGHTED ? "dw_edgelist_parse_weighted" tail : "dw_edgelist_parse" tail)
+template <bool WEIGHTED>
+int parse_text(const uint8_t *text, int64_t n_bytes, int64_t skip_lines,
+               const ParseOut<WEIGHTED> &o, int64_t *counts, int64_t *err_line, int32_t *status,
+               void *workspace, size_t workspace_bytes, void *stream) {
+    Arena a{static_cast<char *>(workspace)};
+    ParseBufs p;
+    int rc = plan_parse(a, n_bytes, &p);
+    if (rc != DW_OK) return rc;
+    DW_REQUIRE(workspace_bytes >= a.off, PARSE_MSG(": workspace too small (%zu < %zu)"),
+               workspace_bytes, a.off);
+    hipStream_t st = dw::as_stream(stream);
+    DW_HIP_OK(hipMemsetAsync(err_line, 0xFF, 8, st), PARSE_MSG(": memset"));   // -1: none
+    DW_HIP_OK(hipMemsetAsync(counts, 0, WEIGHTED ? 24 : 16, st), PARSE_MSG(": memset"));
+    if (n_bytes == 0) return DW_OK;
+    const int64_t n_seg = (n_bytes + PARSE_SEG - 1) / PARSE_SEG;
+    DW_REQUIRE((n_seg + 255) / 256 < LIMIT_31, PARSE_MSG(": chunk too large"));
+    unsigned long long *err = reinterpret_cast<unsigned long long *>(err_line);
+    const dim3 grid(grid_of(n_seg)), block(PARSE_BLOCK);   // (grid_of: blocks of 256)
+    hipLaunchKernelGGL(k_count_lines, grid, block, 0, st, text, n_bytes, n_seg, p.lines_cnt);
+    DW_LAUNCH_CHECK(PARSE_MSG("/lines"));
+    DW_HIP_OK(rocprim::inclusive_scan(p.scan_tmp, p.scan_tmp_bytes,
+                                      static_cast<const uint32_t *>(p.lines_cnt), p.lines_incl,
+                                      static_cast<size_t>(n_seg), rocprim::plus<int64_t>(), st),
+              PARSE_MSG(": line scan"));
+    hipLaunchKernelGGL((k_parse<WEIGHTED, false>), grid, block, 0, st, text, n_bytes, n_seg,
+                       p.lines_incl, p.lines_cnt, skip_lines, p.data_cnt, p.data_incl, o, err,
+                       status);
+    DW_LAUNCH_CHECK(PARSE_MSG("/count"));
+    DW_HIP_OK(rocprim::inclusive_scan(p.scan_tmp, p.scan_tmp_bytes,
+                                      static_cast<const uint32_t *>(p.data_cnt), p.data_incl,
+                                      static_cast<size_t>(n_seg), rocprim::plus<int64_t>(), st),
+              PARSE_MSG(": data scan"));
+    hipLaunchKernelGGL((k_parse<WEIGHTED, true>), grid, block, 0, st, text, n_bytes, n_seg,
+                       p.lines_incl, p.lines_cnt, skip_lines, p.data_cnt, p.data_incl, o, err,
+                       status);
+    DW_LAUNCH_CHECK(PARSE_MSG("/write"));
+    hipLaunchKernelGGL(k_parse_totals, dim3(1), dim3(1), 0, st, p.data_incl, p.lines_incl, n_seg,
+                       counts);
+    DW_LAUNCH_CHECK(PARSE_MSG("/totals"));
+    return DW_OK;
+}
+#undef PARSE_MSG
 
 }  // namespace
 
@@ -517,20 +531,21 @@ int dw_edgelist_workspace_bytes(int64_t n_text_bytes, int64_t n_edges, size_t *b
     DW_REQUIRE(bytes && n_text_bytes >= 0 && n_edges >= 0,
                "dw_edgelist_workspace_bytes: bad arguments");
     DW_REQUIRE(n_edges < LIMIT_31, "dw_edgelist_workspace_bytes: n_edges must be below 2^31");
-    ParsePlan t;
-    CanonPlan c;
-    LoopCsrPlan r;
+    Arena ta{nullptr}, ca{nullptr}, ra{nullptr};
+    ParseBufs t;
+    CanonBufs c;
+    LoopCsrBufs r;
     const int64_t m = n_edges > 0 ? n_edges : 1;
     // (the CSR's node count is not known before dw_edges_canonical: at most min(2 m, 2^31 - 2))
     const int64_t n_max = 2 * m < LIMIT_31 - 2 ? 2 * m : LIMIT_31 - 2;
-    int rc = plan_parse(n_text_bytes, &t);
+    int rc = plan_parse(ta, n_text_bytes, &t);
     if (rc != DW_OK) return rc;
-    rc = plan_canon(m, &c);
+    rc = plan_canon(ca, m, &c);
     if (rc != DW_OK) return rc;
-    rc = plan_loop_csr(m, n_max, &r);
+    rc = plan_loop_csr(ra, m, n_max, &r);
     if (rc != DW_OK) return rc;
-    size_t b = t.total > c.total ? t.total : c.total;
-    *bytes = b > r.total ? b : r.total;
+    size_t b = ta.off > ca.off ? ta.off : ca.off;
+    *bytes = b > ra.off ? b : ra.off;
     return DW_OK;
 }
 
@@ -542,48 +557,8 @@ int dw_edgelist_parse(const uint8_t *text, int64_t n_bytes, int64_t skip_lines, 
     DW_REQUIRE(counts && err_line && status && workspace && (n_bytes == 0 || text) &&
                    (capacity == 0 || (src && dst)),
                "dw_edgelist_parse: null pointer");
-    ParsePlan p;
-    int rc = plan_parse(n_bytes, &p);
-    if (rc != DW_OK) return rc;
-    DW_REQUIRE(workspace_bytes >= p.total, "dw_edgelist_parse: workspace too small (%zu < %zu)",
-               workspace_bytes, p.total);
-    hipStream_t st = dw::as_stream(stream);
-    DW_HIP_OK(hipMemsetAsync(err_line, 0xFF, 8, st), "dw_edgelist_parse: memset");   // -1: none
-    DW_HIP_OK(hipMemsetAsync(counts, 0, 16, st), "dw_edgelist_parse: memset");
-    if (n_bytes == 0) return DW_OK;
-    const int64_t n_seg = (n_bytes + PARSE_SEG - 1) / PARSE_SEG;
-    DW_REQUIRE((n_seg + 255) / 256 < LIMIT_31, "dw_edgelist_parse: chunk too large");
-    char *w = static_cast<char *>(workspace);
-    uint32_t *lines_cnt = reinterpret_cast<uint32_t *>(w + p.lines_cnt);
-    int64_t *lines_incl = reinterpret_cast<int64_t *>(w + p.lines_incl);
-    uint32_t *data_cnt = reinterpret_cast<uint32_t *>(w + p.data_cnt);
-    int64_t *data_incl = reinterpret_cast<int64_t *>(w + p.data_incl);
-    unsigned long long *err = reinterpret_cast<unsigned long long *>(err_line);
-    const dim3 grid(grid_of(n_seg)), block(PARSE_BLOCK);   // (grid_of: blocks of 256)
-    hipLaunchKernelGGL(k_count_lines, grid, block, 0, st, text, n_bytes, n_seg, lines_cnt);
-    DW_LAUNCH_CHECK("dw_edgelist_parse/lines");
-    size_t scan_tmp = p.total - p.scan_tmp;
-    DW_HIP_OK(rocprim::inclusive_scan(w + p.scan_tmp, scan_tmp,
-                                      static_cast<const uint32_t *>(lines_cnt), lines_incl,
-                                      static_cast<size_t>(n_seg), rocprim::plus<int64_t>(), st),
-              "dw_edgelist_parse: line scan");
-    hipLaunchKernelGGL(k_parse<false>, grid, block, 0, st, text, n_bytes, n_seg, lines_incl,
-                       lines_cnt, skip_lines, data_cnt, data_incl, src, dst, capacity, err,
-                       status);
-    DW_LAUNCH_CHECK("dw_edgelist_parse/count");
-    scan_tmp = p.total - p.scan_tmp;
-    DW_HIP_OK(rocprim::inclusive_scan(w + p.scan_tmp, scan_tmp,
-                                      static_cast<const uint32_t *>(data_cnt), data_incl,
-                                      static_cast<size_t>(n_seg), rocprim::plus<int64_t>(), st),
-              "dw_edgelist_parse: data scan");
-    hipLaunchKernelGGL(k_parse<true>, grid, block, 0, st, text, n_bytes, n_seg, lines_incl,
-                       lines_cnt, skip_lines, data_cnt, data_incl, src, dst, capacity, err,
-                       status);
-    DW_LAUNCH_CHECK("dw_edgelist_parse/write");
-    hipLaunchKernelGGL(k_parse_totals, dim3(1), dim3(1), 0, st, data_incl, lines_incl, n_seg,
-                       counts);
-    DW_LAUNCH_CHECK("dw_edgelist_parse/totals");
-    return DW_OK;
+    return parse_text<false>(text, n_bytes, skip_lines, {src, dst, capacity}, counts, err_line,
+                             status, workspace, workspace_bytes, stream);
 }
 
 int dw_edgelist_parse_weighted(const uint8_t *text, int64_t n_bytes, int64_t skip_lines,
@@ -597,50 +572,10 @@ int dw_edgelist_parse_weighted(const uint8_t *text, int64_t n_bytes, int64_t ski
                    (capacity == 0 || (src && dst && weight)) &&
                    (undecided_capacity == 0 || undecided),
                "dw_edgelist_parse_weighted: null pointer");
-    ParsePlan p;
-    int rc = plan_parse(n_bytes, &p);
-    if (rc != DW_OK) return rc;
-    DW_REQUIRE(workspace_bytes >= p.total,
-               "dw_edgelist_parse_weighted: workspace too small (%zu < %zu)", workspace_bytes,
-               p.total);
-    hipStream_t st = dw::as_stream(stream);
-    DW_HIP_OK(hipMemsetAsync(err_line, 0xFF, 8, st), "dw_edgelist_parse_weighted: memset");
-    DW_HIP_OK(hipMemsetAsync(counts, 0, 24, st), "dw_edgelist_parse_weighted: memset");
-    if (n_bytes == 0) return DW_OK;
-    const int64_t n_seg = (n_bytes + PARSE_SEG - 1) / PARSE_SEG;
-    DW_REQUIRE((n_seg + 255) / 256 < LIMIT_31, "dw_edgelist_parse_weighted: chunk too large");
-    char *w = static_cast<char *>(workspace);
-    uint32_t *lines_cnt = reinterpret_cast<uint32_t *>(w + p.lines_cnt);
-    int64_t *lines_incl = reinterpret_cast<int64_t *>(w + p.lines_incl);
-    uint32_t *data_cnt = reinterpret_cast<uint32_t *>(w + p.data_cnt);
-    int64_t *data_incl = reinterpret_cast<int64_t *>(w + p.data_incl);
-    unsigned long long *err = reinterpret_cast<unsigned long long *>(err_line);
-    unsigned long long *n_und = reinterpret_cast<unsigned long long *>(counts + 2);
-    const dim3 grid(grid_of(n_seg)), block(PARSE_BLOCK);
-    hipLaunchKernelGGL(k_count_lines, grid, block, 0, st, text, n_bytes, n_seg, lines_cnt);
-    DW_LAUNCH_CHECK("dw_edgelist_parse_weighted/lines");
-    size_t scan_tmp = p.total - p.scan_tmp;
-    DW_HIP_OK(rocprim::inclusive_scan(w + p.scan_tmp, scan_tmp,
-                                      static_cast<const uint32_t *>(lines_cnt), lines_incl,
-                                      static_cast<size_t>(n_seg), rocprim::plus<int64_t>(), st),
-              "dw_edgelist_parse_weighted: line scan");
-    hipLaunchKernelGGL(k_parse_w<false>, grid, block, 0, st, text, n_bytes, n_seg, lines_incl,
-                       lines_cnt, skip_lines, data_cnt, data_incl, pow5, src, dst, weight,
-                       capacity, undecided, undecided_capacity, n_und, err, status);
-    DW_LAUNCH_CHECK("dw_edgelist_parse_weighted/count");
-    scan_tmp = p.total - p.scan_tmp;
-    DW_HIP_OK(rocprim::inclusive_scan(w + p.scan_tmp, scan_tmp,
-                                      static_cast<const uint32_t *>(data_cnt), data_incl,
-                                      static_cast<size_t>(n_seg), rocprim::plus<int64_t>(), st),
-              "dw_edgelist_parse_weighted: data scan");
-    hipLaunchKernelGGL(k_parse_w<true>, grid, block, 0, st, text, n_bytes, n_seg, lines_incl,
-                       lines_cnt, skip_lines, data_cnt, data_incl, pow5, src, dst, weight,
-                       capacity, undecided, undecided_capacity, n_und, err, status);
-    DW_LAUNCH_CHECK("dw_edgelist_parse_weighted/write");
-    hipLaunchKernelGGL(k_parse_totals, dim3(1), dim3(1), 0, st, data_incl, lines_incl, n_seg,
-                       counts);
-    DW_LAUNCH_CHECK("dw_edgelist_parse_weighted/totals");
-    return DW_OK;
+    return parse_text<true>(text, n_bytes, skip_lines,
+                            {pow5, src, dst, weight, capacity, undecided, undecided_capacity,
+                             reinterpret_cast<unsigned long long *>(counts + 2)},
+                            counts, err_line, status, workspace, workspace_bytes, stream);
 }
 
 int dw_edges_canonical(const int64_t *src, const int64_t *dst, const double *weights,
@@ -652,81 +587,68 @@ int dw_edges_canonical(const int64_t *src, const int64_t *dst, const double *wei
     DW_REQUIRE(src && dst && node_ids && edges && counts && status && workspace &&
                    (!weights || edge_weights),
                "dw_edges_canonical: null pointer");
-    CanonPlan p;
-    int rc = plan_canon(n_edges, &p);
+    Arena a{static_cast<char *>(workspace)};
+    CanonBufs p;
+    int rc = plan_canon(a, n_edges, &p);
     if (rc != DW_OK) return rc;
-    DW_REQUIRE(workspace_bytes >= p.total, "dw_edges_canonical: workspace too small (%zu < %zu)",
-               workspace_bytes, p.total);
+    DW_REQUIRE(workspace_bytes >= a.off, "dw_edges_canonical: workspace too small (%zu < %zu)",
+               workspace_bytes, a.off);
     hipStream_t st = dw::as_stream(stream);
     const int64_t m = n_edges, n2 = 2 * n_edges;
-    char *w = static_cast<char *>(workspace);
-    uint64_t *k0 = reinterpret_cast<uint64_t *>(w + p.keys0);
-    uint64_t *k1 = reinterpret_cast<uint64_t *>(w + p.keys1);
-    uint32_t *p0 = reinterpret_cast<uint32_t *>(w + p.pos0);
-    uint32_t *p1 = reinterpret_cast<uint32_t *>(w + p.pos1);
-    uint32_t *head = reinterpret_cast<uint32_t *>(w + p.head);
-    uint32_t *head_incl = reinterpret_cast<uint32_t *>(w + p.head_incl);
-    uint32_t *rank_of = reinterpret_cast<uint32_t *>(w + p.rank_of);
-    uint64_t *packed = reinterpret_cast<uint64_t *>(w + p.packed);
-    uint8_t *keep = reinterpret_cast<uint8_t *>(w + p.keep);
-    double *w_first = reinterpret_cast<double *>(w + p.w_first);
-    uint32_t *head_pos = reinterpret_cast<uint32_t *>(w + p.head_pos);
-    uint32_t *head_pos_incl = reinterpret_cast<uint32_t *>(w + p.head_pos_incl);
-    int64_t *w_count = reinterpret_cast<int64_t *>(w + p.head_pos_incl + a256(m * 4 + 8) - 8);
-    void *tmp = w + p.tmp;
     size_t tmp_bytes = p.tmp_bytes;
 
     // 1. nodes: sort the 2m endpoints with their positions, rank the runs, scatter ranks back
-    hipLaunchKernelGGL(k_endpoints, dim3(grid_of(m)), dim3(256), 0, st, src, dst, m, id_bits, k0,
-                       p0, status);
+    hipLaunchKernelGGL(k_endpoints, dim3(grid_of(m)), dim3(256), 0, st, src, dst, m, id_bits,
+                       p.keys0, p.pos0, status);
     DW_LAUNCH_CHECK("dw_edges_canonical/endpoints");
-    rocprim::double_buffer<uint64_t> kb(k0, k1);
-    rocprim::double_buffer<uint32_t> vb(p0, p1);
-    DW_HIP_OK(rocprim::radix_sort_pairs(tmp, tmp_bytes, kb, vb, static_cast<size_t>(n2), 0,
+    rocprim::double_buffer<uint64_t> kb(p.keys0, p.keys1);
+    rocprim::double_buffer<uint32_t> vb(p.pos0, p.pos1);
+    DW_HIP_OK(rocprim::radix_sort_pairs(p.tmp, tmp_bytes, kb, vb, static_cast<size_t>(n2), 0,
                                         id_bits, st),
               "dw_edges_canonical: endpoint sort");
-    hipLaunchKernelGGL(k_run_heads, dim3(grid_of(n2)), dim3(256), 0, st, kb.current(), n2, head);
+    hipLaunchKernelGGL(k_run_heads, dim3(grid_of(n2)), dim3(256), 0, st, kb.current(), n2,
+                       p.head);
     DW_LAUNCH_CHECK("dw_edges_canonical/heads");
     tmp_bytes = p.tmp_bytes;
-    DW_HIP_OK(rocprim::inclusive_scan(tmp, tmp_bytes, static_cast<const uint32_t *>(head),
-                                      head_incl, static_cast<size_t>(n2),
+    DW_HIP_OK(rocprim::inclusive_scan(p.tmp, tmp_bytes, static_cast<const uint32_t *>(p.head),
+                                      p.head_incl, static_cast<size_t>(n2),
                                       rocprim::plus<uint32_t>(), st),
               "dw_edges_canonical: rank scan");
     hipLaunchKernelGGL(k_ranks, dim3(grid_of(n2)), dim3(256), 0, st, kb.current(), vb.current(),
-                       head, head_incl, n2, rank_of, node_ids, counts);
+                       p.head, p.head_incl, n2, p.rank_of, node_ids, counts);
     DW_LAUNCH_CHECK("dw_edges_canonical/ranks");
 
     // 2. edges: key (min rank, max rank), stable sort with the raw index, keep every run's head
-    uint64_t *e0 = k0, *e1 = k1;   // (the endpoint buffers are free again)
-    hipLaunchKernelGGL(k_edge_keys, dim3(grid_of(m)), dim3(256), 0, st, rank_of, m, p.rank_bits,
-                       e0, p0, packed);
+    hipLaunchKernelGGL(k_edge_keys, dim3(grid_of(m)), dim3(256), 0, st, p.rank_of, m,
+                       p.rank_bits, p.keys0, p.pos0, p.packed);   // (the endpoint buffers: free)
     DW_LAUNCH_CHECK("dw_edges_canonical/keys");
-    rocprim::double_buffer<uint64_t> eb(e0, e1);
-    rocprim::double_buffer<uint32_t> ib(p0, p1);
+    rocprim::double_buffer<uint64_t> eb(p.keys0, p.keys1);
+    rocprim::double_buffer<uint32_t> ib(p.pos0, p.pos1);
     tmp_bytes = p.tmp_bytes;
-    DW_HIP_OK(rocprim::radix_sort_pairs(tmp, tmp_bytes, eb, ib, static_cast<size_t>(m), 0,
+    DW_HIP_OK(rocprim::radix_sort_pairs(p.tmp, tmp_bytes, eb, ib, static_cast<size_t>(m), 0,
                                         2 * p.rank_bits, st),
               "dw_edges_canonical: edge sort");
     hipLaunchKernelGGL(k_edge_heads, dim3(grid_of(m)), dim3(256), 0, st, eb.current(),
-                       ib.current(), m, keep, weights ? head_pos : nullptr);
+                       ib.current(), m, p.keep, weights ? p.head_pos : nullptr);
     DW_LAUNCH_CHECK("dw_edges_canonical/first");
     tmp_bytes = p.tmp_bytes;
-    DW_HIP_OK(rocprim::select(tmp, tmp_bytes, static_cast<const uint64_t *>(packed),
-                              static_cast<const uint8_t *>(keep), edges, counts + 1,
+    DW_HIP_OK(rocprim::select(p.tmp, tmp_bytes, static_cast<const uint64_t *>(p.packed),
+                              static_cast<const uint8_t *>(p.keep), edges, counts + 1,
                               static_cast<size_t>(m), st),
               "dw_edges_canonical: edge select");
     if (weights) {
         tmp_bytes = p.tmp_bytes;
-        DW_HIP_OK(rocprim::inclusive_scan(tmp, tmp_bytes, static_cast<const uint32_t *>(head_pos),
-                                          head_pos_incl, static_cast<size_t>(m),
+        DW_HIP_OK(rocprim::inclusive_scan(p.tmp, tmp_bytes,
+                                          static_cast<const uint32_t *>(p.head_pos),
+                                          p.head_pos_incl, static_cast<size_t>(m),
                                           rocprim::maximum<uint32_t>(), st),
                   "dw_edges_canonical: head scan");
         hipLaunchKernelGGL(k_tail_weights, dim3(grid_of(m)), dim3(256), 0, st, eb.current(),
-                           ib.current(), head_pos_incl, weights, m, w_first);
+                           ib.current(), p.head_pos_incl, weights, m, p.w_first);
         DW_LAUNCH_CHECK("dw_edges_canonical/weights");
         tmp_bytes = p.tmp_bytes;
-        DW_HIP_OK(rocprim::select(tmp, tmp_bytes, static_cast<const double *>(w_first),
-                                  static_cast<const uint8_t *>(keep), edge_weights, w_count,
+        DW_HIP_OK(rocprim::select(p.tmp, tmp_bytes, static_cast<const double *>(p.w_first),
+                                  static_cast<const uint8_t *>(p.keep), edge_weights, p.w_count,
                                   static_cast<size_t>(m), st),
                   "dw_edges_canonical: weight select");
     }
@@ -742,39 +664,33 @@ int dw_csr_from_edges_loops(const uint64_t *edges, const double *edge_weights, i
     DW_REQUIRE(row_ptr && status && workspace && (n_edges == 0 || (edges && col)) &&
                    (!edge_weights || weights || n_edges == 0),
                "dw_csr_from_edges_loops: null pointer");
-    LoopCsrPlan p;
-    int rc = plan_loop_csr(n_edges > 0 ? n_edges : 1, n_nodes, &p);
+    Arena a{static_cast<char *>(workspace)};
+    LoopCsrBufs p;
+    int rc = plan_loop_csr(a, n_edges > 0 ? n_edges : 1, n_nodes, &p);
     if (rc != DW_OK) return rc;
-    DW_REQUIRE(workspace_bytes >= p.total,
+    DW_REQUIRE(workspace_bytes >= a.off,
                "dw_csr_from_edges_loops: workspace too small (%zu < %zu)", workspace_bytes,
-               p.total);
+               a.off);
     hipStream_t st = dw::as_stream(stream);
-    char *w = static_cast<char *>(workspace);
-    uint32_t *deg = reinterpret_cast<uint32_t *>(w + p.deg);
-    void *tmp = w + p.tmp;
-    DW_HIP_OK(hipMemsetAsync(deg, 0, n_nodes * 4, st), "dw_csr_from_edges_loops: memset");
-    hipLaunchKernelGGL(k_row_ptr_head2, dim3(1), dim3(1), 0, st, row_ptr);
+    DW_HIP_OK(hipMemsetAsync(p.deg, 0, n_nodes * 4, st), "dw_csr_from_edges_loops: memset");
+    hipLaunchKernelGGL(k_row_ptr_head, dim3(1), dim3(1), 0, st, row_ptr);
     DW_LAUNCH_CHECK("dw_csr_from_edges_loops/head");
     const int64_t n2 = 2 * n_edges;
-    uint32_t *k0 = reinterpret_cast<uint32_t *>(w + p.keys0);
-    uint32_t *k1 = reinterpret_cast<uint32_t *>(w + p.keys1);
-    uint32_t *v0 = reinterpret_cast<uint32_t *>(w + p.vals0);
-    uint32_t *v1 = reinterpret_cast<uint32_t *>(w + p.vals1);
-    rocprim::double_buffer<uint32_t> kb(k0, k1), vb(v0, v1);
+    rocprim::double_buffer<uint32_t> kb(p.keys0, p.keys1), vb(p.vals0, p.vals1);
     if (n_edges > 0) {
-        hipLaunchKernelGGL(k_degree_loops, dim3(grid_of(n_edges)), dim3(256), 0, st, edges,
-                           n_edges, n_nodes, deg, status);
+        hipLaunchKernelGGL(k_degree<true>, dim3(grid_of(n_edges)), dim3(256), 0, st, edges,
+                           n_edges, n_nodes, p.deg, status);
         DW_LAUNCH_CHECK("dw_csr_from_edges_loops/degree");
         hipLaunchKernelGGL(k_entries_loops, dim3(grid_of(n_edges)), dim3(256), 0, st, edges,
-                           n_edges, n_nodes, k0, v0);
+                           n_edges, n_nodes, p.keys0, p.vals0);
         DW_LAUNCH_CHECK("dw_csr_from_edges_loops/entries");
         size_t tmp_bytes = p.tmp_bytes;
-        DW_HIP_OK(rocprim::radix_sort_pairs(tmp, tmp_bytes, kb, vb, static_cast<size_t>(n2), 0,
+        DW_HIP_OK(rocprim::radix_sort_pairs(p.tmp, tmp_bytes, kb, vb, static_cast<size_t>(n2), 0,
                                             bits_for(n_nodes + 1), st),
                   "dw_csr_from_edges_loops: sort");
     }
     size_t tmp_bytes = p.tmp_bytes;
-    DW_HIP_OK(rocprim::inclusive_scan(tmp, tmp_bytes, static_cast<const uint32_t *>(deg),
+    DW_HIP_OK(rocprim::inclusive_scan(p.tmp, tmp_bytes, static_cast<const uint32_t *>(p.deg),
                                       row_ptr + 2, static_cast<size_t>(n_nodes),
                                       rocprim::plus<int64_t>(), st),
               "dw_csr_from_edges_loops: scan");

@@ -1,5 +1,6 @@
-// Host-side helpers shared by the graph-ingestion sources (dw_rmat.hip, dw_edgelist.hip): the
-// workspace layout arithmetic and the HIP error check of their rocprim calls. Not part of the ABI.
+// Helpers shared by the graph-ingestion sources (dw_rmat.hip, dw_edgelist.hip): the workspace
+// arena, the HIP error check of their rocprim calls and the two kernels both CSR builders start
+// with. Not part of the ABI.
 #pragma once
 
 #include "dw_common.h"
@@ -16,6 +17,51 @@ inline int bits_for(int64_t n) {  // bits of values < n
 }
 
 inline unsigned grid_of(int64_t n) { return static_cast<unsigned>((n + 255) / 256); }
+
+// A workspace handed out piece by piece, each piece starting on a 256-byte boundary. A plan
+// function names every buffer of an entry point once, as a take<T>(n): run on a null base it
+// hands out nothing and `off` ends as the bytes the entry point needs (the *_workspace_bytes
+// queries); run on the caller's workspace it gives the typed pointers, and `off` is what the
+// workspace must hold (checked before any of them is used).
+struct Arena {
+    char *base;
+    size_t off = 0;
+    template <class T>
+    T *take(size_t n) {
+        T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
+        off += a256(n * sizeof(T));
+        return p;
+    }
+    // The last T of the piece handed out last: room its take() counted in behind the array.
+    template <class T>
+    T *last() const {
+        return base ? reinterpret_cast<T *>(base + off) - 1 : nullptr;
+    }
+};
+
+// row_ptr[0] = row_ptr[1] = 0: row 0 is <unk>; the degree scan fills row_ptr[2:].
+static __global__ void k_row_ptr_head(int64_t *row_ptr) {
+    row_ptr[0] = 0;
+    row_ptr[1] = 0;
+}
+
+// Degree of every endpoint of the packed edges (u << 32 | v). LOOPS: a self-loop is one entry
+// (dw_csr_from_edges_loops); without it the callers' edges hold none and both ends count.
+template <bool LOOPS>
+static __global__ void __launch_bounds__(256)
+    k_degree(const uint64_t *__restrict__ edges, int64_t m, int64_t n_nodes,
+             uint32_t *__restrict__ deg, int32_t *status) {
+    const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (i >= m) return;
+    const uint64_t e = edges[i];
+    const uint64_t u = e >> 32, v = e & 0xFFFFFFFFull;
+    if (u >= static_cast<uint64_t>(n_nodes) || v >= static_cast<uint64_t>(n_nodes)) {
+        dw::status_or(status, DW_S_BAD_CSR);
+        return;
+    }
+    atomicAdd(deg + u, 1u);
+    if (!LOOPS || u != v) atomicAdd(deg + v, 1u);
+}
 
 }  // namespace ingest
 }  // namespace dw

@@ -109,21 +109,6 @@ __global__ void __launch_bounds__(256)
 }
 
 __global__ void __launch_bounds__(256)
-    k_endpoint_degree(const uint64_t *__restrict__ edges, int64_t m, int64_t n_nodes,
-                      uint32_t *__restrict__ deg, int32_t *status) {
-    const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
-    if (i >= m) return;
-    const uint64_t e = edges[i];
-    const uint64_t u = e >> 32, v = e & 0xFFFFFFFFull;
-    if (u >= static_cast<uint64_t>(n_nodes) || v >= static_cast<uint64_t>(n_nodes)) {
-        dw::status_or(status, DW_S_BAD_CSR);
-        return;
-    }
-    atomicAdd(deg + u, 1u);
-    atomicAdd(deg + v, 1u);
-}
-
-__global__ void __launch_bounds__(256)
     k_zero_flags(const uint32_t *__restrict__ deg, int64_t n, uint8_t *__restrict__ flag) {
     const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
     if (i < n) flag[i] = deg[i] == 0u ? 1 : 0;
@@ -143,77 +128,77 @@ __global__ void __launch_bounds__(256)
     vals[2 * i + 1] = u + 1u;
 }
 
-__global__ void k_row_ptr_head(int64_t *row_ptr) {
-    row_ptr[0] = 0;
-    row_ptr[1] = 0;
-}
-
-using dw::ingest::a256;   // (shared with dw_edgelist.hip: dw_ingest.h)
+using dw::ingest::Arena;   // (shared with dw_edgelist.hip: dw_ingest.h)
 using dw::ingest::bits_for;
 using dw::ingest::grid_of;
+using dw::ingest::k_degree;
+using dw::ingest::k_row_ptr_head;
 
 // ---- workspace plans (one size serves the three calls) ----------------------------------------
-struct RmatPlan {
-    size_t raw, keys0, keys1, idx0, idx1, keep, sort_tmp, sel_tmp, total;
+struct RmatBufs {
+    uint64_t *raw, *keys0, *keys1;
+    uint32_t *idx0, *idx1;
+    uint8_t *keep;
+    char *sort_tmp, *sel_tmp;
+    size_t sort_tmp_bytes, sel_tmp_bytes;
 };
 
-int plan_rmat(int32_t scale, int64_t n, RmatPlan *p) {
-    size_t sort_tmp = 0, sel_tmp = 0;
+int plan_rmat(Arena &a, int32_t scale, int64_t n, RmatBufs *p) {
     rocprim::double_buffer<uint64_t> kb(nullptr, nullptr);
     rocprim::double_buffer<uint32_t> vb(nullptr, nullptr);
-    DW_HIP_OK(rocprim::radix_sort_pairs(nullptr, sort_tmp, kb, vb, static_cast<uint32_t>(n), 0,
+    DW_HIP_OK(rocprim::radix_sort_pairs(nullptr, p->sort_tmp_bytes, kb, vb,
+                                        static_cast<uint32_t>(n), 0,
                                         2 * scale + 1),
               "dw_rmat: sort size query");
-    DW_HIP_OK(rocprim::select(nullptr, sel_tmp, static_cast<const uint64_t *>(nullptr),
+    DW_HIP_OK(rocprim::select(nullptr, p->sel_tmp_bytes, static_cast<const uint64_t *>(nullptr),
                               static_cast<const uint8_t *>(nullptr),
                               static_cast<uint64_t *>(nullptr), static_cast<int64_t *>(nullptr),
                               static_cast<size_t>(n)),
               "dw_rmat: select size query");
-    size_t off = 0;
-    p->raw = off;   off += a256(n * 8);
-    p->keys0 = off; off += a256(n * 8);
-    p->keys1 = off; off += a256(n * 8);
-    p->idx0 = off;  off += a256(n * 4);
-    p->idx1 = off;  off += a256(n * 4);
-    p->keep = off;  off += a256(n);
-    p->sort_tmp = off; off += a256(sort_tmp);
-    p->sel_tmp = off;  off += a256(sel_tmp);
-    p->total = off;
+    p->raw = a.take<uint64_t>(n);
+    p->keys0 = a.take<uint64_t>(n);
+    p->keys1 = a.take<uint64_t>(n);
+    p->idx0 = a.take<uint32_t>(n);
+    p->idx1 = a.take<uint32_t>(n);
+    p->keep = a.take<uint8_t>(n);
+    p->sort_tmp = a.take<char>(p->sort_tmp_bytes);
+    p->sel_tmp = a.take<char>(p->sel_tmp_bytes);
     return DW_OK;
 }
 
-struct CsrPlan {
-    size_t keys0, keys1, vals0, vals1, deg, flags, sort_tmp, scan_tmp, sel_tmp, total;
+struct CsrBufs {
+    uint32_t *keys0, *keys1, *vals0, *vals1, *deg;
+    uint8_t *flags;
+    char *sort_tmp, *scan_tmp, *sel_tmp;
+    size_t sort_tmp_bytes, scan_tmp_bytes, sel_tmp_bytes;
 };
 
-int plan_csr(int64_t m, int64_t n_nodes, CsrPlan *p) {
+int plan_csr(Arena &a, int64_t m, int64_t n_nodes, CsrBufs *p) {
     const int64_t nnz = 2 * m;
-    size_t sort_tmp = 0, scan_tmp = 0, sel_tmp = 0;
     rocprim::double_buffer<uint32_t> kb(nullptr, nullptr), vb(nullptr, nullptr);
-    DW_HIP_OK(rocprim::radix_sort_pairs(nullptr, sort_tmp, kb, vb,
+    DW_HIP_OK(rocprim::radix_sort_pairs(nullptr, p->sort_tmp_bytes, kb, vb,
                                         static_cast<uint32_t>(nnz > 0 ? nnz : 1), 0,
                                         bits_for(n_nodes)),
               "dw_csr_from_edges: sort size query");
-    DW_HIP_OK(rocprim::inclusive_scan(nullptr, scan_tmp, static_cast<const uint32_t *>(nullptr),
+    DW_HIP_OK(rocprim::inclusive_scan(nullptr, p->scan_tmp_bytes,
+                                      static_cast<const uint32_t *>(nullptr),
                                       static_cast<int64_t *>(nullptr),
                                       static_cast<size_t>(n_nodes), rocprim::plus<int64_t>()),
               "dw_csr_from_edges: scan size query");
-    DW_HIP_OK(rocprim::select(nullptr, sel_tmp, rocprim::counting_iterator<int32_t>(0),
+    DW_HIP_OK(rocprim::select(nullptr, p->sel_tmp_bytes, rocprim::counting_iterator<int32_t>(0),
                               static_cast<const uint8_t *>(nullptr),
                               static_cast<int32_t *>(nullptr), static_cast<int64_t *>(nullptr),
                               static_cast<size_t>(n_nodes)),
               "dw_graph_isolated: select size query");
-    size_t off = 0;
-    p->keys0 = off; off += a256(nnz * 4);
-    p->keys1 = off; off += a256(nnz * 4);
-    p->vals0 = off; off += a256(nnz * 4);
-    p->vals1 = off; off += a256(nnz * 4);
-    p->deg = off;   off += a256(n_nodes * 4);
-    p->flags = off; off += a256(n_nodes);
-    p->sort_tmp = off; off += a256(sort_tmp);
-    p->scan_tmp = off; off += a256(scan_tmp);
-    p->sel_tmp = off;  off += a256(sel_tmp);
-    p->total = off;
+    p->keys0 = a.take<uint32_t>(nnz);
+    p->keys1 = a.take<uint32_t>(nnz);
+    p->vals0 = a.take<uint32_t>(nnz);
+    p->vals1 = a.take<uint32_t>(nnz);
+    p->deg = a.take<uint32_t>(n_nodes);
+    p->flags = a.take<uint8_t>(n_nodes);
+    p->sort_tmp = a.take<char>(p->sort_tmp_bytes);
+    p->scan_tmp = a.take<char>(p->scan_tmp_bytes);
+    p->sel_tmp = a.take<char>(p->sel_tmp_bytes);
     return DW_OK;
 }
 
@@ -226,13 +211,14 @@ int dw_ingest_workspace_bytes(int32_t scale, int64_t n_edges, int64_t n_nodes, s
                "dw_ingest_workspace_bytes: bad arguments");
     DW_REQUIRE(n_edges < (int64_t(1) << 31) && n_nodes < (int64_t(1) << 31),
                "dw_ingest_workspace_bytes: sizes must fit int32");
-    RmatPlan r;
-    CsrPlan c;
-    int rc = plan_rmat(scale, n_edges > 0 ? n_edges : 1, &r);
+    Arena ra{nullptr}, ca{nullptr};
+    RmatBufs r;
+    CsrBufs c;
+    int rc = plan_rmat(ra, scale, n_edges > 0 ? n_edges : 1, &r);
     if (rc != DW_OK) return rc;
-    rc = plan_csr(n_edges > 0 ? n_edges : 1, n_nodes, &c);
+    rc = plan_csr(ca, n_edges > 0 ? n_edges : 1, n_nodes, &c);
     if (rc != DW_OK) return rc;
-    *bytes = r.total > c.total ? r.total : c.total;
+    *bytes = ra.off > ca.off ? ra.off : ca.off;
     return DW_OK;
 }
 
@@ -244,38 +230,30 @@ int dw_rmat_edges(int32_t scale, int64_t n_edges, const uint64_t *level_state,
                "dw_rmat_edges: bad sizes");
     DW_REQUIRE(level_state && jump && edges && n_unique && workspace,
                "dw_rmat_edges: null pointer");
-    RmatPlan p;
-    int rc = plan_rmat(scale, n_edges, &p);
+    Arena a{static_cast<char *>(workspace)};
+    RmatBufs p;
+    int rc = plan_rmat(a, scale, n_edges, &p);
     if (rc != DW_OK) return rc;
-    DW_REQUIRE(workspace_bytes >= p.total, "dw_rmat_edges: workspace too small (%zu < %zu)",
-               workspace_bytes, p.total);
+    DW_REQUIRE(workspace_bytes >= a.off, "dw_rmat_edges: workspace too small (%zu < %zu)",
+               workspace_bytes, a.off);
     hipStream_t st = dw::as_stream(stream);
-    char *w = static_cast<char *>(workspace);
-    uint64_t *raw = reinterpret_cast<uint64_t *>(w + p.raw);
     const int64_t n_threads = (n_edges + RMAT_EDGES_PER_THREAD - 1) / RMAT_EDGES_PER_THREAD;
     hipLaunchKernelGGL(k_rmat_draw, dim3(grid_of(n_threads)), dim3(256), 0, st, scale, n_edges,
-                       level_state, jump, U128{inc_lo, inc_hi}, t1, t2, t3, raw);
+                       level_state, jump, U128{inc_lo, inc_hi}, t1, t2, t3, p.raw);
     DW_LAUNCH_CHECK("dw_rmat_edges/draw");
-    uint64_t *k0 = reinterpret_cast<uint64_t *>(w + p.keys0);
-    uint64_t *k1 = reinterpret_cast<uint64_t *>(w + p.keys1);
-    uint32_t *i0 = reinterpret_cast<uint32_t *>(w + p.idx0);
-    uint32_t *i1 = reinterpret_cast<uint32_t *>(w + p.idx1);
-    uint8_t *keep = reinterpret_cast<uint8_t *>(w + p.keep);
-    hipLaunchKernelGGL(k_rmat_keys, dim3(grid_of(n_edges)), dim3(256), 0, st, raw, n_edges,
-                       scale, k0, i0);
+    hipLaunchKernelGGL(k_rmat_keys, dim3(grid_of(n_edges)), dim3(256), 0, st, p.raw, n_edges,
+                       scale, p.keys0, p.idx0);
     DW_LAUNCH_CHECK("dw_rmat_edges/keys");
-    rocprim::double_buffer<uint64_t> kb(k0, k1);
-    rocprim::double_buffer<uint32_t> vb(i0, i1);
-    size_t sort_tmp = p.sel_tmp - p.sort_tmp;
-    DW_HIP_OK(rocprim::radix_sort_pairs(w + p.sort_tmp, sort_tmp, kb, vb,
+    rocprim::double_buffer<uint64_t> kb(p.keys0, p.keys1);
+    rocprim::double_buffer<uint32_t> vb(p.idx0, p.idx1);
+    DW_HIP_OK(rocprim::radix_sort_pairs(p.sort_tmp, p.sort_tmp_bytes, kb, vb,
                                         static_cast<uint32_t>(n_edges), 0, 2 * scale + 1, st),
               "dw_rmat_edges: sort");
     hipLaunchKernelGGL(k_rmat_first, dim3(grid_of(n_edges)), dim3(256), 0, st, kb.current(),
-                       vb.current(), n_edges, 1ull << (2 * scale), keep);
+                       vb.current(), n_edges, 1ull << (2 * scale), p.keep);
     DW_LAUNCH_CHECK("dw_rmat_edges/first");
-    size_t sel_tmp = p.total - p.sel_tmp;
-    DW_HIP_OK(rocprim::select(w + p.sel_tmp, sel_tmp, static_cast<const uint64_t *>(raw),
-                              static_cast<const uint8_t *>(keep), edges, n_unique,
+    DW_HIP_OK(rocprim::select(p.sel_tmp, p.sel_tmp_bytes, static_cast<const uint64_t *>(p.raw),
+                              static_cast<const uint8_t *>(p.keep), edges, n_unique,
                               static_cast<size_t>(n_edges), st),
               "dw_rmat_edges: compaction");
     return DW_OK;
@@ -288,26 +266,23 @@ int dw_graph_isolated(const uint64_t *edges, int64_t n_edges, int64_t n_nodes,
                "dw_graph_isolated: bad sizes");
     DW_REQUIRE(isolated && n_isolated && status && workspace && (edges || n_edges == 0),
                "dw_graph_isolated: null pointer");
-    CsrPlan p;
-    int rc = plan_csr(n_edges > 0 ? n_edges : 1, n_nodes, &p);
+    Arena a{static_cast<char *>(workspace)};
+    CsrBufs p;
+    int rc = plan_csr(a, n_edges > 0 ? n_edges : 1, n_nodes, &p);
     if (rc != DW_OK) return rc;
-    DW_REQUIRE(workspace_bytes >= p.total, "dw_graph_isolated: workspace too small");
+    DW_REQUIRE(workspace_bytes >= a.off, "dw_graph_isolated: workspace too small");
     hipStream_t st = dw::as_stream(stream);
-    char *w = static_cast<char *>(workspace);
-    uint32_t *deg = reinterpret_cast<uint32_t *>(w + p.deg);
-    uint8_t *flags = reinterpret_cast<uint8_t *>(w + p.flags);
-    DW_HIP_OK(hipMemsetAsync(deg, 0, n_nodes * 4, st), "dw_graph_isolated: memset");
+    DW_HIP_OK(hipMemsetAsync(p.deg, 0, n_nodes * 4, st), "dw_graph_isolated: memset");
     if (n_edges > 0) {
-        hipLaunchKernelGGL(k_endpoint_degree, dim3(grid_of(n_edges)), dim3(256), 0, st, edges,
-                           n_edges, n_nodes, deg, status);
+        hipLaunchKernelGGL(k_degree<false>, dim3(grid_of(n_edges)), dim3(256), 0, st, edges,
+                           n_edges, n_nodes, p.deg, status);
         DW_LAUNCH_CHECK("dw_graph_isolated/degree");
     }
-    hipLaunchKernelGGL(k_zero_flags, dim3(grid_of(n_nodes)), dim3(256), 0, st, deg, n_nodes,
-                       flags);
+    hipLaunchKernelGGL(k_zero_flags, dim3(grid_of(n_nodes)), dim3(256), 0, st, p.deg, n_nodes,
+                       p.flags);
     DW_LAUNCH_CHECK("dw_graph_isolated/flags");
-    size_t sel_tmp = p.total - p.sel_tmp;
-    DW_HIP_OK(rocprim::select(w + p.sel_tmp, sel_tmp, rocprim::counting_iterator<int32_t>(0),
-                              static_cast<const uint8_t *>(flags), isolated, n_isolated,
+    DW_HIP_OK(rocprim::select(p.sel_tmp, p.sel_tmp_bytes, rocprim::counting_iterator<int32_t>(0),
+                              static_cast<const uint8_t *>(p.flags), isolated, n_isolated,
                               static_cast<size_t>(n_nodes), st),
               "dw_graph_isolated: compaction");
     return DW_OK;
@@ -321,41 +296,34 @@ int dw_csr_from_edges(const uint64_t *edges, int64_t n_edges, int64_t n_nodes,
                "dw_csr_from_edges: bad sizes");
     DW_REQUIRE(row_ptr && status && workspace && (n_edges == 0 || (edges && col)),
                "dw_csr_from_edges: null pointer");
-    CsrPlan p;
-    int rc = plan_csr(n_edges > 0 ? n_edges : 1, n_nodes, &p);
+    Arena a{static_cast<char *>(workspace)};
+    CsrBufs p;
+    int rc = plan_csr(a, n_edges > 0 ? n_edges : 1, n_nodes, &p);
     if (rc != DW_OK) return rc;
-    DW_REQUIRE(workspace_bytes >= p.total, "dw_csr_from_edges: workspace too small");
+    DW_REQUIRE(workspace_bytes >= a.off, "dw_csr_from_edges: workspace too small");
     hipStream_t st = dw::as_stream(stream);
-    char *w = static_cast<char *>(workspace);
-    uint32_t *deg = reinterpret_cast<uint32_t *>(w + p.deg);
-    DW_HIP_OK(hipMemsetAsync(deg, 0, n_nodes * 4, st), "dw_csr_from_edges: memset");
+    DW_HIP_OK(hipMemsetAsync(p.deg, 0, n_nodes * 4, st), "dw_csr_from_edges: memset");
     hipLaunchKernelGGL(k_row_ptr_head, dim3(1), dim3(1), 0, st, row_ptr);
     DW_LAUNCH_CHECK("dw_csr_from_edges/head");
     if (n_edges > 0) {
-        hipLaunchKernelGGL(k_endpoint_degree, dim3(grid_of(n_edges)), dim3(256), 0, st, edges,
-                           n_edges, n_nodes, deg, status);
+        hipLaunchKernelGGL(k_degree<false>, dim3(grid_of(n_edges)), dim3(256), 0, st, edges,
+                           n_edges, n_nodes, p.deg, status);
         DW_LAUNCH_CHECK("dw_csr_from_edges/degree");
         const int64_t nnz = 2 * n_edges;
-        uint32_t *k0 = reinterpret_cast<uint32_t *>(w + p.keys0);
-        uint32_t *k1 = reinterpret_cast<uint32_t *>(w + p.keys1);
-        uint32_t *v0 = reinterpret_cast<uint32_t *>(w + p.vals0);
-        uint32_t *v1 = reinterpret_cast<uint32_t *>(w + p.vals1);
         hipLaunchKernelGGL(k_csr_entries, dim3(grid_of(n_edges)), dim3(256), 0, st, edges,
-                           n_edges, k0, v0);
+                           n_edges, p.keys0, p.vals0);
         DW_LAUNCH_CHECK("dw_csr_from_edges/entries");
-        rocprim::double_buffer<uint32_t> kb(k0, k1), vb(v0, v1);
-        size_t sort_tmp = p.scan_tmp - p.sort_tmp;
-        DW_HIP_OK(rocprim::radix_sort_pairs(w + p.sort_tmp, sort_tmp, kb, vb,
+        rocprim::double_buffer<uint32_t> kb(p.keys0, p.keys1), vb(p.vals0, p.vals1);
+        DW_HIP_OK(rocprim::radix_sort_pairs(p.sort_tmp, p.sort_tmp_bytes, kb, vb,
                                             static_cast<uint32_t>(nnz), 0, bits_for(n_nodes),
                                             st),
                   "dw_csr_from_edges: sort");
         DW_HIP_OK(hipMemcpyAsync(col, vb.current(), nnz * 4, hipMemcpyDeviceToDevice, st),
                   "dw_csr_from_edges: copy");
     }
-    size_t scan_tmp = p.sel_tmp - p.scan_tmp;
-    DW_HIP_OK(rocprim::inclusive_scan(w + p.scan_tmp, scan_tmp, static_cast<const uint32_t *>(deg),
-                                      row_ptr + 2, static_cast<size_t>(n_nodes),
-                                      rocprim::plus<int64_t>(), st),
+    DW_HIP_OK(rocprim::inclusive_scan(p.scan_tmp, p.scan_tmp_bytes,
+                                      static_cast<const uint32_t *>(p.deg), row_ptr + 2,
+                                      static_cast<size_t>(n_nodes), rocprim::plus<int64_t>(), st),
               "dw_csr_from_edges: scan");
     return DW_OK;
 }

@@ -365,59 +365,52 @@ def read_edge_arrays(path: str, device=None, skip_rows: int = 0,
     srcs, dsts, wtss, lines_seen = [], [], [], 0
     for n in _text_chunks(path, stage):
         skip = max(0, skip_rows - lines_seen)
-        if on_device and weighted:
+        if on_device:
             with torch.cuda.device(dev):
                 text[:n].copy_(stage_t[:n], non_blocking=True)
-                _native.call('dw_edgelist_parse_weighted', _native.ptr(text), n, skip,
-                             _native.ptr(pow5), _native.ptr(sbuf), _native.ptr(dbuf),
-                             _native.ptr(wbuf), cap, _native.ptr(ubuf), undecided_capacity,
-                             _native.ptr(info), _native.ptr(info[3:]), _native.ptr(status),
-                             _native.ptr(ws), ws.numel(), _native.stream(dev))
-                k, n_lines, n_und, bad = (int(x) for x in info.tolist())   # synchronises
-                # the first offence of the chunk, in file order: a bad line or an infinite weight
+                tail = (_native.ptr(info), _native.ptr(info[-1:]), _native.ptr(status),
+                        _native.ptr(ws), ws.numel(), _native.stream(dev))
+                if weighted:
+                    _native.call('dw_edgelist_parse_weighted', _native.ptr(text), n, skip,
+                                 _native.ptr(pow5), _native.ptr(sbuf), _native.ptr(dbuf),
+                                 _native.ptr(wbuf), cap, _native.ptr(ubuf), undecided_capacity,
+                                 *tail)
+                else:
+                    _native.call('dw_edgelist_parse', _native.ptr(text), n, skip,
+                                 _native.ptr(sbuf), _native.ptr(dbuf), cap, *tail)
+                counts = [int(x) for x in info.tolist()]   # synchronises: stage is free
+                k, n_lines, bad = counts[0], counts[1], counts[-1]
+                # the first offence of the chunk, in file order: a bad line or (weighted) an
+                # infinite weight
                 first = None
                 if int(status.item()) & _native.DW_S_BAD_TEXT:
+                    what = 'a weighted edge' if weighted else 'an edge'
                     first = (lines_seen + bad + 1,
-                             f'{path}: line {lines_seen + bad + 1} is not a weighted edge')
-                w_chunk = wbuf[:k]
-                if n_und > undecided_capacity:   # the host twin raises for either offence itself
-                    w_host = parse_lines_host(stage[:n].tobytes(), skip, lines_seen + 1, path,
-                                              weighted=True)[2]
-                    w_chunk = torch.from_numpy(w_host).to(dev)
-                elif n_und:
-                    inf = _patch_undecided(ubuf[:2 * n_und].cpu().numpy().reshape(-1, 2), stage,
-                                           n, wbuf, path, lines_seen)
-                    if inf is not None and (first is None or inf[0] < first[0]):
-                        first = inf
+                             f'{path}: line {lines_seen + bad + 1} is not {what}')
+                if weighted:
+                    n_und = counts[2]
+                    w_chunk = wbuf[:k]
+                    if n_und > undecided_capacity:   # the host twin raises for either offence
+                        w_host = parse_lines_host(stage[:n].tobytes(), skip, lines_seen + 1, path,
+                                                  weighted=True)[2]
+                        w_chunk = torch.from_numpy(w_host).to(dev)
+                    elif n_und:
+                        inf = _patch_undecided(ubuf[:2 * n_und].cpu().numpy().reshape(-1, 2),
+                                               stage, n, wbuf, path, lines_seen)
+                        if inf is not None and (first is None or inf[0] < first[0]):
+                            first = inf
                 if first is not None:
                     raise ValueError(first[1])
                 _native.check_status(status, 'edge-list parse')
                 srcs.append(sbuf[:k].clone())
                 dsts.append(dbuf[:k].clone())
-                wtss.append(w_chunk.clone())
-        elif on_device:
-            with torch.cuda.device(dev):
-                text[:n].copy_(stage_t[:n], non_blocking=True)
-                _native.call('dw_edgelist_parse', _native.ptr(text), n, skip, _native.ptr(sbuf),
-                             _native.ptr(dbuf), cap, _native.ptr(info), _native.ptr(info[2:]),
-                             _native.ptr(status), _native.ptr(ws), ws.numel(),
-                             _native.stream(dev))
-                k, n_lines, bad = (int(x) for x in info.tolist())   # synchronises: stage is free
-                if int(status.item()) & _native.DW_S_BAD_TEXT:
-                    raise ValueError(f'{path}: line {lines_seen + bad + 1} is not an edge')
-                _native.check_status(status, 'edge-list parse')
-                srcs.append(sbuf[:k].clone())
-                dsts.append(dbuf[:k].clone())
-        elif weighted:
-            s, d, w, n_lines = parse_lines_host(stage[:n].tobytes(), skip, lines_seen + 1, path,
-                                                weighted=True)
-            srcs.append(s)
-            dsts.append(d)
-            wtss.append(w)
+                if weighted:
+                    wtss.append(w_chunk.clone())
         else:
-            s, d, n_lines = parse_lines_host(stage[:n].tobytes(), skip, lines_seen + 1, path)
-            srcs.append(s)
-            dsts.append(d)
+            *arrays, n_lines = parse_lines_host(stage[:n].tobytes(), skip, lines_seen + 1, path,
+                                                weighted=weighted)
+            for acc, x in zip((srcs, dsts, wtss), arrays):
+                acc.append(x)
         lines_seen += n_lines
     if on_device:
         if not srcs:

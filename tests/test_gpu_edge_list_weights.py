@@ -215,6 +215,81 @@ def test_tokens_across_segment_stage_and_overrun_edges(hip_device):
     assert got['status'] == _native.DW_S_BAD_TEXT and got['bad'] == _n_lines(long) - 2
 
 
+def _device_parse_ids(data: bytes, dev):
+    """dw_edgelist_parse (the id-only instantiation) on its own: src, dst, lines, bad, status."""
+    n = len(data)
+    cap = (n + 1) // 4 + 1
+    with torch.cuda.device(dev):
+        text = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev)
+        nb = ctypes.c_size_t(0)
+        _native.call('dw_edgelist_workspace_bytes', n, 0, ctypes.byref(nb))
+        ws = torch.empty(int(nb.value), dtype=torch.uint8, device=dev)
+        src = torch.full((cap,), -7, dtype=torch.int64, device=dev)
+        dst = torch.full((cap,), -7, dtype=torch.int64, device=dev)
+        info = torch.zeros(3, dtype=torch.int64, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        _native.call('dw_edgelist_parse', _native.ptr(text), n, 0, _native.ptr(src),
+                     _native.ptr(dst), cap, _native.ptr(info), _native.ptr(info[2:]),
+                     _native.ptr(status), _native.ptr(ws), ws.numel(), _native.stream(dev))
+        k, lines, bad = info.tolist()
+    assert (src[k:] == -7).all() and (dst[k:] == -7).all()
+    return src[:k].tolist(), dst[:k].tolist(), lines, bad, int(status.item())
+
+
+def test_both_parsers_agree_where_the_second_id_ends_at_an_edge(hip_device):
+    """The two grammars are one function (parse_line<WEIGHTED>), so a slip in the prefix they
+    share would move both parsers together: one "u v w" text, just past a stage and its overrun,
+    goes through dw_edgelist_parse (the weight is an extra column) and dw_edgelist_parse_weighted;
+    both equal each other and parse_lines_host where the second id — the last field they share —
+    ends at a segment's edge and at the stage's edge, and for a line that starts in the overrun."""
+    rng = np.random.default_rng(17)
+    forms = [b'1e3', b'-0', b'.5', b'5.', b'+2.5E-3']
+    parts, toks = [b'# u v w\n', b'\n', b' \t\n', b'% a comment\n', b'\r\n'], []
+
+    def add(u, v, tok, end=b'\n'):
+        parts.append(b'%d %d %s' % (u, v, tok) + end)
+        toks.append(tok)
+
+    def lines_until(limit):   # random lines, then one comment line up to ``limit`` exactly
+        i = 0
+        while sum(len(p) for p in parts) + 100 < limit:
+            u, v = rng.integers(0, 10 ** 6, size=2).tolist()
+            tok = forms[i // 9 % len(forms)] if i % 9 == 4 else repr(rng.random() + 0.5).encode()
+            add(u, v, tok, b'\r\n' if i % 5 == 2 else b'\n')
+            if i % 11 == 7:
+                parts.append(b'\n' if i % 2 else b'  # between\n')
+            i += 1
+        _fill_to(parts, limit)
+
+    seg_edge = 64 * 97
+    lines_until(seg_edge - 7)
+    add(11, 2222, b'0.5')                    # '11 2222': the separator behind it is at the edge
+    lines_until(STAGE - 7)
+    add(33, 4444, b'1.25', b'\r\n')
+    in_overrun = sum(len(p) for p in parts)  # the next line starts behind the stage's edge
+    add(55, 66, b'7.75')
+    lines_until(STAGE + OVER + 300)
+    add(77, 88, b'0.1')
+    data = b''.join(parts)
+    assert STAGE + OVER < len(data) < STAGE + OVER + 1024
+    for edge in (seg_edge, STAGE):
+        assert data[edge - 4:edge + 1] in (b'2222 ', b'4444 ')
+    assert STAGE < in_overrun < STAGE + OVER and data[in_overrun - 1:in_overrun + 5] == b'\n55 66'
+    hs, hd, h_lines = el.parse_lines_host(data)
+    ws, wd, ww, w_lines = el.parse_lines_host(data, weighted=True)
+    assert len(hs) == len(toks) > 500 and h_lines == w_lines == _n_lines(data)
+    assert (ws.tolist(), wd.tolist()) == (hs.tolist(), hd.tolist())
+    assert ww.view(np.uint64).tolist() == [sref.float_bits(t) for t in toks]
+    assert all(sref.token_bits(t) == sref.float_bits(t) for t in toks)   # none is undecided
+    ids = _device_parse_ids(data, hip_device)
+    assert ids == (hs.tolist(), hd.tolist(), h_lines, -1, 0)
+    got = device_parse(data, hip_device)
+    assert got['status'] == 0 and got['bad'] == -1
+    assert (got['src'], got['dst'], got['lines']) == ids[:3]
+    assert got['w'] == [sref.float_bits(t) for t in toks]   # float(token), bit for bit
+    assert got['n_und'] == 0 and got['und'] == []
+
+
 # ---- chunks -----------------------------------------------------------------------------------------
 def _undecided_lines(n, seed):
     """n lines; every seventh weight is one the kernel hands back (subnormal / 25 digits that the
