@@ -48,6 +48,39 @@ __device__ __forceinline__ int32_t eff_step(const dw_step_scalars *dyn, int32_t 
 
 static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
+// ---- workspaces -----------------------------------------------------------------------------
+inline size_t a256(size_t x) { return (x + 255) & ~size_t(255); }
+
+// A workspace handed out piece by piece, each piece starting on a 256-byte boundary. A plan
+// function names every buffer of an entry point once, as a take<T>(n): run on a null base it
+// hands out nothing and `off` ends as the bytes the entry point needs (the *_workspace_bytes
+// queries); run on the caller's workspace it gives the typed pointers, and `off` is what the
+// workspace must hold (checked before any of them is used).
+struct Arena {
+    char *base;
+    size_t off = 0;
+    template <class T>
+    T *take(size_t n) {
+        T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
+        off += a256(n * sizeof(T));
+        return p;
+    }
+    // The last T of the piece handed out last: room its take() counted in behind the array.
+    template <class T>
+    T *last() const {
+        return base ? reinterpret_cast<T *>(base + off) - 1 : nullptr;
+    }
+};
+
+// The window of the walks forms (a centre needs R positions on either side), refused in the
+// reference's words under the caller's name.
+inline int require_window(const char *who, int32_t walk_length, int32_t context_radius) {
+    DW_REQUIRE(context_radius >= 1, "%s: context_radius must be >= 1", who);
+    DW_REQUIRE(walk_length >= 2 * context_radius + 1,
+               "%s: walk_length %d < 2R+1 (Text is too short!)", who, walk_length);
+    return DW_OK;
+}
+
 // ---- Philox4x32-10 (Salmon et al., SC'11), the device RNG of every fast-mode kernel ----------
 // Restated bit-for-bit on the host in oracle/philox.py (test infrastructure).
 struct U4 {

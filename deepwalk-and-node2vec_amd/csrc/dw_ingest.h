@@ -1,6 +1,6 @@
-// Helpers shared by the graph-ingestion sources (dw_rmat.hip, dw_edgelist.hip): the workspace
-// arena, the HIP error check of their rocprim calls and the two kernels both CSR builders start
-// with. Not part of the ABI.
+// Helpers shared by the graph-ingestion sources (dw_rmat.hip, dw_edgelist.hip): the HIP error
+// check of their rocprim calls and the two kernels both CSR builders start with. Not part of the
+// ABI.
 #pragma once
 
 #include "dw_common.h"
@@ -8,7 +8,7 @@
 namespace dw {
 namespace ingest {
 
-inline size_t a256(size_t x) { return (x + 255) & ~size_t(255); }
+using dw::Arena;   // the workspace arena (dw_common.h)
 
 inline int bits_for(int64_t n) {  // bits of values < n
     int b = 1;
@@ -17,27 +17,6 @@ inline int bits_for(int64_t n) {  // bits of values < n
 }
 
 inline unsigned grid_of(int64_t n) { return static_cast<unsigned>((n + 255) / 256); }
-
-// A workspace handed out piece by piece, each piece starting on a 256-byte boundary. A plan
-// function names every buffer of an entry point once, as a take<T>(n): run on a null base it
-// hands out nothing and `off` ends as the bytes the entry point needs (the *_workspace_bytes
-// queries); run on the caller's workspace it gives the typed pointers, and `off` is what the
-// workspace must hold (checked before any of them is used).
-struct Arena {
-    char *base;
-    size_t off = 0;
-    template <class T>
-    T *take(size_t n) {
-        T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
-        off += a256(n * sizeof(T));
-        return p;
-    }
-    // The last T of the piece handed out last: room its take() counted in behind the array.
-    template <class T>
-    T *last() const {
-        return base ? reinterpret_cast<T *>(base + off) - 1 : nullptr;
-    }
-};
 
 // row_ptr[0] = row_ptr[1] = 0: row 0 is <unk>; the degree scan fills row_ptr[2:].
 static __global__ void k_row_ptr_head(int64_t *row_ptr) {

@@ -29,6 +29,7 @@
 #include <atomic>
 #include <cmath>
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -1209,12 +1210,11 @@ struct Workspace {
     uint32_t *count;  // records of the owner form (dw_sgns_owner_pass1), after compaction
     uint32_t *wave_counts;   // [MAX_OWNER_WAVES] records per pass-1 wave region (owner form)
     int64_t *wave_offsets;   // [MAX_OWNER_WAVES] their exclusive prefix sums
-    void *cub;
+    char *cub;        // the records sort's temporary storage
     size_t cub_bytes;
-    size_t total;
 };
 
-inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
+using dw::Arena;   // (dw_common.h: every buffer of a plan is one take<T>(n))
 
 // Records sort: onesweep with 11-bit digits on 1024 x 16 tiles — 2 passes for C3's 21-bit row
 // ids (the gfx950 default, 8-bit digits on 1024 x 8, needs 3): 0.79 ms vs 1.09 ms for 34.4M
@@ -1275,36 +1275,26 @@ hipError_t sort_pairs(void *tmp, size_t &bytes, rocprim::double_buffer<K> &kb,
     return rocprim::radix_sort_pairs<RecordSortConfig>(tmp, bytes, kb, vb, n, 0, end_bit, st);
 }
 
-int plan_workspace(int64_t n_rec, int64_t V, void *base, Workspace *ws, hipStream_t st) {
-    size_t cub_bytes = 0;
+// The records part, first in every workspace: the key / value double buffers of the sort, the
+// piece bounds, the owner form's counters and the sort's temporary storage.
+int plan_workspace(Arena &a, int64_t n_rec, int64_t V, Workspace *ws, hipStream_t st) {
     rocprim::double_buffer<uint32_t> kb(nullptr, nullptr);
     rocprim::double_buffer<uint64_t> vb(nullptr, nullptr);
-    hipError_t e = sort_pairs(nullptr, cub_bytes, kb, vb, static_cast<uint32_t>(n_rec),
+    hipError_t e = sort_pairs(nullptr, ws->cub_bytes, kb, vb, static_cast<uint32_t>(n_rec),
                               end_bit_for(V), st);
     if (e != hipSuccess) {
         dw::set_error("dw_sgns: sort size query failed: %s", hipGetErrorString(e));
         return DW_E_HIP;
     }
-    const size_t kbytes = align256((size_t)n_rec * 4), vbytes = align256((size_t)n_rec * 8);
-    char *p = static_cast<char *>(base);
-    ws->k0 = reinterpret_cast<uint32_t *>(p);
-    ws->k1 = reinterpret_cast<uint32_t *>(p + kbytes);
-    ws->v0 = reinterpret_cast<uint64_t *>(p + 2 * kbytes);
-    ws->v1 = reinterpret_cast<uint64_t *>(p + 2 * kbytes + vbytes);
-    const size_t wbytes = align256(sizeof(uint32_t) * MAX_OWNER_WAVES) +
-                          align256(sizeof(int64_t) * MAX_OWNER_WAVES);
-    const size_t bbytes = align256(sizeof(int64_t) * (MAX_PIECES + 1)) + 256 + wbytes;
-    char *q = p + 2 * kbytes + 2 * vbytes;
-    ws->bounds = reinterpret_cast<int64_t *>(q);
-    q += align256(sizeof(int64_t) * (MAX_PIECES + 1));
-    ws->count = reinterpret_cast<uint32_t *>(q);
-    q += 256;
-    ws->wave_counts = reinterpret_cast<uint32_t *>(q);
-    q += align256(sizeof(uint32_t) * MAX_OWNER_WAVES);
-    ws->wave_offsets = reinterpret_cast<int64_t *>(q);
-    ws->cub = p + 2 * kbytes + 2 * vbytes + bbytes;
-    ws->cub_bytes = cub_bytes;
-    ws->total = 2 * kbytes + 2 * vbytes + bbytes + align256(cub_bytes);
+    ws->k0 = a.take<uint32_t>(n_rec);
+    ws->k1 = a.take<uint32_t>(n_rec);
+    ws->v0 = a.take<uint64_t>(n_rec);
+    ws->v1 = a.take<uint64_t>(n_rec);
+    ws->bounds = a.take<int64_t>(MAX_PIECES + 1);
+    ws->count = a.take<uint32_t>(1);   // (a 256-byte slot of its own)
+    ws->wave_counts = a.take<uint32_t>(MAX_OWNER_WAVES);
+    ws->wave_offsets = a.take<int64_t>(MAX_OWNER_WAVES);
+    ws->cub = a.take<char>(ws->cub_bytes);
     return DW_OK;
 }
 
@@ -1322,6 +1312,41 @@ int64_t grid_cap(int per_cu) {
         n_cu[dev] = v;
     }
     return (int64_t)n_cu[dev] * per_cu;
+}
+
+// Blocks of a launch over n items, `per` to a block: ceil(n / per) within [lo, cap] (lo = 0: no
+// lower clamp — the caller launches nothing for n = 0).
+inline unsigned grid_for(int64_t n, int64_t per, int64_t lo, int64_t cap) {
+    int64_t blocks = (n + per - 1) / per;
+    if (blocks > cap) blocks = cap;
+    if (blocks < lo) blocks = lo;
+    return static_cast<unsigned>(blocks);
+}
+
+// One dispatch on the embedding width. W is the least of {1, 2, 4, 8} with d <= 64 W: the VPL of
+// the 64-lane kernels (elements per lane, MASKED when d < 64 W) and the F4 of the 16-lane ones
+// (float4s per lane; they take d = 64 W only, `whole`, and CHR = 8 / F4 rows per chunk).
+// f(W, MASKED, EXACT) gets the three as std::integral_constant and names its kernel once;
+// returns f's status, or DW_E_UNSUPPORTED with no error text (each caller keeps its own way out)
+// when d > 512 or, with `whole`, d < 64 W.
+template <int W, class F>
+int for_width_w(int32_t d, bool exact, F &&f) {
+    const std::integral_constant<int, W> w{};
+    if (d != 64 * W)
+        return exact ? f(w, std::true_type{}, std::true_type{})
+                     : f(w, std::true_type{}, std::false_type{});
+    return exact ? f(w, std::false_type{}, std::true_type{})
+                 : f(w, std::false_type{}, std::false_type{});
+}
+
+template <class F>
+int for_width(int32_t d, bool whole, bool exact, F &&f) {
+    if (d > 512 || (whole && !(d == 64 || d == 128 || d == 256 || d == 512)))
+        return DW_E_UNSUPPORTED;
+    if (d <= 64) return for_width_w<1>(d, exact, f);
+    if (d <= 128) return for_width_w<2>(d, exact, f);
+    if (d <= 256) return for_width_w<4>(d, exact, f);
+    return for_width_w<8>(d, exact, f);
 }
 
 // ---- deterministic mode: gradient buffers with an int64 fixed-point accumulator -------------
@@ -1370,40 +1395,22 @@ namespace {
 
 template <bool FROM_WALKS, bool RECORDS>
 int launch_pass1(const SgnsArgs &a, hipStream_t st) {
-    int64_t blocks = (a.batch + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-    if (blocks > grid_cap(8)) blocks = grid_cap(8);
-    if (blocks < 1) blocks = 1;
-    const dim3 g((unsigned)blocks), bl(WAVES_PER_BLOCK * WAVE);
+    const dim3 g(grid_for(a.batch, WAVES_PER_BLOCK, 1, grid_cap(8))), bl(WAVES_PER_BLOCK * WAVE);
     const bool exact = a.fx_in.acc != nullptr;
     DW_REQUIRE(!exact || RECORDS, "dw_sgns: the deterministic mode needs the records (sorted) "
                "output-table path");
     DW_REQUIRE(!exact || FROM_WALKS || a.n_in == 1,
                "dw_sgns: the deterministic mode does not cover pooled (CBOW) inputs");
-#define DW_SGNS_CASE(VPL)                                                                    \
-    if (a.d <= 64 * VPL) {                                                                    \
-        const bool full = a.d == 64 * VPL;                                                    \
-        if (exact && RECORDS && full)                                                         \
-            hipLaunchKernelGGL((k_sgns<VPL, false, FROM_WALKS, RECORDS, CHUNK, RECORDS>), g,  \
-                               bl, 0, st, a);                                                 \
-        else if (exact && RECORDS)                                                            \
-            hipLaunchKernelGGL((k_sgns<VPL, true, FROM_WALKS, RECORDS, CHUNK, RECORDS>), g,   \
-                               bl, 0, st, a);                                                 \
-        else if (full)                                                                        \
-            hipLaunchKernelGGL((k_sgns<VPL, false, FROM_WALKS, RECORDS, CHUNK>), g, bl, 0, st, \
-                               a);                                                            \
-        else                                                                                  \
-            hipLaunchKernelGGL((k_sgns<VPL, true, FROM_WALKS, RECORDS, CHUNK>), g, bl, 0, st, \
-                               a);                                                            \
-        DW_LAUNCH_CHECK("dw_sgns");                                                           \
-        return DW_OK;                                                                         \
-    }
-    DW_SGNS_CASE(1)
-    DW_SGNS_CASE(2)
-    DW_SGNS_CASE(4)
-    DW_SGNS_CASE(8)
-#undef DW_SGNS_CASE
-    dw::set_error("dw_sgns: dim %d > 512 is not supported", a.d);
-    return DW_E_UNSUPPORTED;
+    const int rc = for_width(a.d, false, exact, [&](auto w, auto masked, auto x) -> int {
+        constexpr int VPL = decltype(w)::value;
+        constexpr bool MASKED = decltype(masked)::value, EXACT = RECORDS && decltype(x)::value;
+        hipLaunchKernelGGL((k_sgns<VPL, MASKED, FROM_WALKS, RECORDS, CHUNK, EXACT>), g, bl, 0, st,
+                           a);
+        DW_LAUNCH_CHECK("dw_sgns");
+        return DW_OK;
+    });
+    if (rc == DW_E_UNSUPPORTED) dw::set_error("dw_sgns: dim %d > 512 is not supported", a.d);
+    return rc;
 }
 
 // 16-lane-group pass 1 when d is a multiple of 64 (<= 512) and 2R(1+K) <= 64; otherwise
@@ -1412,62 +1419,32 @@ template <bool FROM_WALKS, bool OWNER = false, bool COEFIN = false>
 int launch_pass1_g16(const SgnsArgs &a, hipStream_t st) {
     const int64_t T = (int64_t)a.C * (1 + a.K);
     if (a.d % 64 != 0 || a.d > 512 || T > G16_TMAX) return DW_E_UNSUPPORTED;
-    int64_t blocks = (a.batch + 4 * WAVES_PER_BLOCK - 1) / (4 * WAVES_PER_BLOCK);
-    if (blocks > grid_cap(8)) blocks = grid_cap(8);
-    if (blocks < 1) blocks = 1;
-    const dim3 g((unsigned)blocks), bl(WAVES_PER_BLOCK * WAVE);
-    if constexpr (COEFIN) {
-        // (eight and sixteen rows per chunk measured 45 and 59 us against 42 at C3's 64-walk
-        // batch: the pass-1 chunking stays)
-        switch ((a.d / 64) * 2 + (a.fx_in.acc ? 1 : 0)) {
-            case 2: hipLaunchKernelGGL((k_sgns_g16<1, FROM_WALKS, 8, true, false, true>), g, bl, 0, st, a); break;
-            case 3: hipLaunchKernelGGL((k_sgns_g16<1, FROM_WALKS, 8, true, true, true>), g, bl, 0, st, a); break;
-            case 4: hipLaunchKernelGGL((k_sgns_g16<2, FROM_WALKS, 4, true, false, true>), g, bl, 0, st, a); break;
-            case 5: hipLaunchKernelGGL((k_sgns_g16<2, FROM_WALKS, 4, true, true, true>), g, bl, 0, st, a); break;
-            case 8: hipLaunchKernelGGL((k_sgns_g16<4, FROM_WALKS, 2, true, false, true>), g, bl, 0, st, a); break;
-            case 9: hipLaunchKernelGGL((k_sgns_g16<4, FROM_WALKS, 2, true, true, true>), g, bl, 0, st, a); break;
-            case 16: hipLaunchKernelGGL((k_sgns_g16<8, FROM_WALKS, 1, true, false, true>), g, bl, 0, st, a); break;
-            case 17: hipLaunchKernelGGL((k_sgns_g16<8, FROM_WALKS, 1, true, true, true>), g, bl, 0, st, a); break;
-            default:
-                dw::set_error("dw_sgns: the coefficient-input pass 1 needs d in {64, 128, 256, 512}, got %d", a.d);
-                return DW_E_UNSUPPORTED;
-        }
-        DW_LAUNCH_CHECK("dw_sgns/g16_coefin");
-        return DW_OK;
-    }
-    if (a.fx_in.acc) {   // deterministic mode
-        switch (a.d / 64) {
-            case 1: hipLaunchKernelGGL((k_sgns_g16<1, FROM_WALKS, 8, OWNER, true>), g, bl, 0, st, a); break;
-            case 2: hipLaunchKernelGGL((k_sgns_g16<2, FROM_WALKS, 4, OWNER, true>), g, bl, 0, st, a); break;
-            case 4: hipLaunchKernelGGL((k_sgns_g16<4, FROM_WALKS, 2, OWNER, true>), g, bl, 0, st, a); break;
-            case 8: hipLaunchKernelGGL((k_sgns_g16<8, FROM_WALKS, 1, OWNER, true>), g, bl, 0, st, a); break;
-            default: return DW_E_UNSUPPORTED;   // the caller falls back to k_sgns
-        }
-        DW_LAUNCH_CHECK("dw_sgns/g16");
-        return DW_OK;
-    }
-    if constexpr (FROM_WALKS && !OWNER) {
-        if (a.coef_pos) {   // walk aggregation (plan_walks): positive coefficients, not records
-            switch (a.d / 64) {
-                case 1: hipLaunchKernelGGL((k_sgns_g16<1, true, 8, false, false, false, true>), g, bl, 0, st, a); break;
-                case 2: hipLaunchKernelGGL((k_sgns_g16<2, true, 4, false, false, false, true>), g, bl, 0, st, a); break;
-                case 4: hipLaunchKernelGGL((k_sgns_g16<4, true, 2, false, false, false, true>), g, bl, 0, st, a); break;
-                case 8: hipLaunchKernelGGL((k_sgns_g16<8, true, 1, false, false, false, true>), g, bl, 0, st, a); break;
-                default: return DW_E_UNSUPPORTED;
+    const dim3 g(grid_for(a.batch, 4 * WAVES_PER_BLOCK, 1, grid_cap(8))),
+        bl(WAVES_PER_BLOCK * WAVE);
+    // (COEFIN: eight and sixteen rows per chunk measured 45 and 59 us against 42 at C3's 64-walk
+    // batch: the pass-1 chunking stays)
+    const int rc = for_width(a.d, true, a.fx_in.acc != nullptr, [&](auto f4, auto, auto x) -> int {
+        constexpr int F4 = decltype(f4)::value;
+        constexpr int CHR = 8 / F4;   // rows per chunk: CHR * F4 float4 registers per lane
+        constexpr bool EXACT = decltype(x)::value;   // the deterministic mode
+        if constexpr (FROM_WALKS && !OWNER && !COEFIN && !EXACT) {
+            if (a.coef_pos) {   // walk aggregation (plan_walks): positive coefficients, not records
+                hipLaunchKernelGGL((k_sgns_g16<F4, true, CHR, false, false, false, true>), g, bl, 0,
+                                   st, a);
+                DW_LAUNCH_CHECK("dw_sgns/g16_agg");
+                return DW_OK;
             }
-            DW_LAUNCH_CHECK("dw_sgns/g16_agg");
-            return DW_OK;
         }
-    }
-    switch (a.d / 64) {  // rows per chunk: CHR * F4 float4 registers per lane
-        case 1: hipLaunchKernelGGL((k_sgns_g16<1, FROM_WALKS, 8, OWNER>), g, bl, 0, st, a); break;
-        case 2: hipLaunchKernelGGL((k_sgns_g16<2, FROM_WALKS, 4, OWNER>), g, bl, 0, st, a); break;
-        case 4: hipLaunchKernelGGL((k_sgns_g16<4, FROM_WALKS, 2, OWNER>), g, bl, 0, st, a); break;
-        case 8: hipLaunchKernelGGL((k_sgns_g16<8, FROM_WALKS, 1, OWNER>), g, bl, 0, st, a); break;
-        default: return DW_E_UNSUPPORTED;   // the caller falls back to k_sgns
-    }
-    DW_LAUNCH_CHECK("dw_sgns/g16");
-    return DW_OK;
+        hipLaunchKernelGGL((k_sgns_g16<F4, FROM_WALKS, CHR, OWNER, EXACT, COEFIN>), g, bl, 0, st,
+                           a);
+        DW_LAUNCH_CHECK(COEFIN ? "dw_sgns/g16_coefin" : "dw_sgns/g16");
+        return DW_OK;
+    });
+    // d of 192, 320, 384 or 448 is no kernel's: the caller falls back to k_sgns where it can
+    if (COEFIN && rc == DW_E_UNSUPPORTED)
+        dw::set_error("dw_sgns: the coefficient-input pass 1 needs d in {64, 128, 256, 512}, "
+                      "got %d", a.d);
+    return rc;
 }
 
 // Rows the fused gather did not update: boundary rows (g in g_out) and rows no record touched
@@ -1557,22 +1534,6 @@ __global__ void __launch_bounds__(WAVES_PER_BLOCK *WAVE)
         lazy_row_step<VPL, MASKED>(oa, dw::eff_step(oa.dyn, oa.step_delta, oa.step), row, d,
                                    lane, g);
     }
-}
-
-template <int VPL>
-void launch_boundary(hipStream_t st, const uint32_t *keys, int64_t n_rec, int32_t gch,
-                     float *g_out, int32_t d, const OutAdam &oa, const int64_t *range) {
-    int64_t blocks = ((n_rec + gch - 1) / gch + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-    if (blocks < 1) blocks = 1;
-    if (blocks > 65536) blocks = 65536;
-    if (d == 64 * VPL)
-        hipLaunchKernelGGL((k_lazy_boundary<VPL, false>), dim3((unsigned)blocks),
-                           dim3(WAVES_PER_BLOCK * WAVE), 0, st, keys, n_rec, gch, g_out, d, oa,
-                           range);
-    else
-        hipLaunchKernelGGL((k_lazy_boundary<VPL, true>), dim3((unsigned)blocks),
-                           dim3(WAVES_PER_BLOCK * WAVE), 0, st, keys, n_rec, gch, g_out, d, oa,
-                           range);
 }
 
 // ---- the rows-major lazy out step (dw_sgns_owner_out_rows) -----------------------------------
@@ -1858,56 +1819,6 @@ __global__ void __launch_bounds__(WAVES_PER_BLOCK *WAVE, F4 <= 2 ? OUT_ROWS_WAVE
     if (a.loss_acc) flush_loss(a.loss_acc, acc_pos, acc_neg, acc_rec, acc_prec);
 }
 
-template <int VPL, bool EXACT>
-void launch_gather_fx(dim3 g, dim3 bl, hipStream_t st, const uint32_t *keys,
-                      const uint64_t *vals, int64_t n_rec, const float *w_in, float *g_out,
-                      int32_t d, const OutAdam *oa, const int64_t *range, int32_t gch,
-                      const dw::Fixed &fo, int32_t *status, const float *agg) {
-    const bool full = d == 64 * VPL;
-    if (oa) {
-        if (full)
-            hipLaunchKernelGGL((k_rec_gather<VPL, false, true, EXACT>), g, bl, 0, st, keys, vals,
-                               n_rec, w_in, g_out, d, *oa, range, gch, fo, status, agg);
-        else
-            hipLaunchKernelGGL((k_rec_gather<VPL, true, true, EXACT>), g, bl, 0, st, keys, vals,
-                               n_rec, w_in, g_out, d, *oa, range, gch, fo, status, agg);
-    } else {
-        if (full)
-            hipLaunchKernelGGL((k_rec_gather<VPL, false, false, EXACT>), g, bl, 0, st, keys,
-                               vals, n_rec, w_in, g_out, d, OutAdam{}, range, gch, fo, status,
-                               agg);
-        else
-            hipLaunchKernelGGL((k_rec_gather<VPL, true, false, EXACT>), g, bl, 0, st, keys, vals,
-                               n_rec, w_in, g_out, d, OutAdam{}, range, gch, fo, status, agg);
-    }
-}
-
-template <int VPL>
-void launch_gather(dim3 g, dim3 bl, hipStream_t st, const uint32_t *keys, const uint64_t *vals,
-                   int64_t n_rec, const float *w_in, float *g_out, int32_t d,
-                   const OutAdam *oa, const int64_t *range, int32_t gch, const dw::Fixed &fo,
-                   int32_t *status, const float *agg) {
-    if (fo.acc)
-        launch_gather_fx<VPL, true>(g, bl, st, keys, vals, n_rec, w_in, g_out, d, oa, range, gch,
-                                    fo, status, agg);
-    else
-        launch_gather_fx<VPL, false>(g, bl, st, keys, vals, n_rec, w_in, g_out, d, oa, range,
-                                     gch, fo, status, agg);
-}
-
-template <int VPL>
-void launch_rest(hipStream_t st, int64_t V, int32_t d, float *g_out, const OutAdam &oa) {
-    int64_t rb = (V + 255) / 256;   // 4 waves x 64 rows per block
-    if (rb > grid_cap(8)) rb = grid_cap(8);
-    if (rb < 1) rb = 1;
-    if (d == 64 * VPL)
-        hipLaunchKernelGGL((k_adam_rest<VPL, false>), dim3((unsigned)rb), dim3(256), 0, st, V, d,
-                           oa.flags, g_out, oa);
-    else
-        hipLaunchKernelGGL((k_adam_rest<VPL, true>), dim3((unsigned)rb), dim3(256), 0, st, V, d,
-                           oa.flags, g_out, oa);
-}
-
 // oa != NULL: the fused output-table Adam (rows 0..V of the out table) — gather, then the
 // rest-of-rows update, which also clears the row flags.
 // range != NULL: one row piece (records [range[0], range[1]), read on the device); the grid is
@@ -1935,30 +1846,41 @@ int launch_pass2(const uint32_t *keys, const uint64_t *vals, int64_t n_rec, cons
     if (blocks < 1) blocks = 1;
     if (blocks > 65536) blocks = 65536;
     const dim3 g((unsigned)blocks), bl(WAVES_PER_BLOCK * WAVE);
-    if (d <= 64) launch_gather<1>(g, bl, st, keys, vals, n_rec, w_in, g_out, d, oa, range, gch, fo, status, agg);
-    else if (d <= 128) launch_gather<2>(g, bl, st, keys, vals, n_rec, w_in, g_out, d, oa, range, gch, fo, status, agg);
-    else if (d <= 256) launch_gather<4>(g, bl, st, keys, vals, n_rec, w_in, g_out, d, oa, range, gch, fo, status, agg);
-    else if (d <= 512) launch_gather<8>(g, bl, st, keys, vals, n_rec, w_in, g_out, d, oa, range, gch, fo, status, agg);
-    else return DW_E_UNSUPPORTED;
-    DW_LAUNCH_CHECK("dw_sgns/gather");
+    const int rc = for_width(d, false, fo.acc != nullptr, [&](auto w, auto masked, auto x) -> int {
+        constexpr int VPL = decltype(w)::value;
+        constexpr bool MASKED = decltype(masked)::value, EXACT = decltype(x)::value;
+        if (oa)
+            hipLaunchKernelGGL((k_rec_gather<VPL, MASKED, true, EXACT>), g, bl, 0, st, keys, vals,
+                               n_rec, w_in, g_out, d, *oa, range, gch, fo, status, agg);
+        else
+            hipLaunchKernelGGL((k_rec_gather<VPL, MASKED, false, EXACT>), g, bl, 0, st, keys, vals,
+                               n_rec, w_in, g_out, d, OutAdam{}, range, gch, fo, status, agg);
+        DW_LAUNCH_CHECK("dw_sgns/gather");
+        return DW_OK;
+    });
+    if (rc != DW_OK) return rc;
     if (fo.acc && n_rec > 0) {   // the straddling rows' exact sums into g_out
         hipLaunchKernelGGL(k_fixed_boundary, g, bl, 0, st, keys, n_rec, gch, range, fo, g_out, d);
         DW_LAUNCH_CHECK("dw_sgns/fixed_boundary");
     }
     if (oa && oa->last) {   // lazy: only the straddling rows remain; untouched rows wait
-        if (n_rec > 0) {
-            if (d <= 64) launch_boundary<1>(st, keys, n_rec, gch, g_out, d, *oa, range);
-            else if (d <= 128) launch_boundary<2>(st, keys, n_rec, gch, g_out, d, *oa, range);
-            else if (d <= 256) launch_boundary<4>(st, keys, n_rec, gch, g_out, d, *oa, range);
-            else launch_boundary<8>(st, keys, n_rec, gch, g_out, d, *oa, range);
+        if (n_rec == 0) return DW_OK;
+        const dim3 gb(grid_for(n_chunks, WAVES_PER_BLOCK, 1, 65536));
+        return for_width(d, false, false, [&](auto w, auto masked, auto) -> int {
+            hipLaunchKernelGGL((k_lazy_boundary<decltype(w)::value, decltype(masked)::value>), gb,
+                               bl, 0, st, keys, n_rec, gch, g_out, d, *oa, range);
             DW_LAUNCH_CHECK("dw_sgns/lazy_boundary");
-        }
-    } else if (oa) {
-        if (d <= 64) launch_rest<1>(st, V, d, g_out, *oa);
-        else if (d <= 128) launch_rest<2>(st, V, d, g_out, *oa);
-        else if (d <= 256) launch_rest<4>(st, V, d, g_out, *oa);
-        else launch_rest<8>(st, V, d, g_out, *oa);
-        DW_LAUNCH_CHECK("dw_sgns/adam_rest");   // (k_adam_rest also clears the flags)
+            return DW_OK;
+        });
+    }
+    if (oa) {   // the rest of the rows: 4 waves x 64 rows per block (k_adam_rest clears the flags)
+        const dim3 gr(grid_for(V, 256, 1, grid_cap(8)));
+        return for_width(d, false, false, [&](auto w, auto masked, auto) -> int {
+            hipLaunchKernelGGL((k_adam_rest<decltype(w)::value, decltype(masked)::value>), gr,
+                               dim3(256), 0, st, V, d, oa->flags, g_out, *oa);
+            DW_LAUNCH_CHECK("dw_sgns/adam_rest");
+            return DW_OK;
+        });
     }
     return DW_OK;
 }
@@ -2041,38 +1963,30 @@ struct WalkPlan {
     int64_t n_neg, n_rec;
     Workspace ws;
     float *coef_pos, *agg_rows;
-    size_t total;
 };
 
-int plan_walks(int64_t n_walks, int32_t L, int32_t R, int32_t K, int64_t V, int32_t d, bool agg,
-               void *base, WalkPlan *p, hipStream_t st) {
+int plan_walks(Arena &a, int64_t n_walks, int32_t L, int32_t R, int32_t K, int64_t V, int32_t d,
+               bool agg, WalkPlan *p, hipStream_t st) {
     const int64_t batch = n_walks * (L - 2 * R), C = 2 * R;
     p->agg = agg;
     p->n_neg = agg ? batch * C * K : 0;
     p->n_rec = agg ? p->n_neg + n_walks * L : batch * C * (1 + (int64_t)K);
     DW_REQUIRE(p->n_rec < 0x7FFFFFFF, "dw_sgns: records mode needs fewer than 2^31 records");
-    const int rc = plan_workspace(p->n_rec > 0 ? p->n_rec : 1, V, base, &p->ws, st);
+    const int rc = plan_workspace(a, p->n_rec > 0 ? p->n_rec : 1, V, &p->ws, st);
     if (rc != DW_OK) return rc;
-    p->total = p->ws.total;
-    p->coef_pos = p->agg_rows = nullptr;
-    if (agg) {
-        char *b = static_cast<char *>(base);
-        p->coef_pos = reinterpret_cast<float *>(b + p->total);
-        p->total += align256(static_cast<size_t>(batch * C) * 4);
-        p->agg_rows = reinterpret_cast<float *>(b + p->total);
-        p->total += align256(static_cast<size_t>(n_walks * L) * d * 4);
-    }
+    p->coef_pos = agg ? a.take<float>(batch * C) : nullptr;
+    p->agg_rows = agg ? a.take<float>(n_walks * L * d) : nullptr;
     return DW_OK;
 }
 
 // A walks call's plan from its arguments alone (phase 1, phase 2, the fused-Adam phase 2 and the
 // pieces are separate calls and must agree). The accumulators of the deterministic mode are
 // registered on both gradient buffers or on neither (a call without g_in tests g_out's).
-int plan_walks_for(const SgnsArgs &a, void *base, WalkPlan *p, hipStream_t st) {
+int plan_walks_for(const SgnsArgs &a, Arena &ar, WalkPlan *p, hipStream_t st) {
     const int64_t n_walks = a.batch / (a.L - 2 * a.R);
     const bool exact = exact_registered(a.g_out) || exact_registered(a.g_in);
-    return plan_walks(n_walks, a.L, a.R, a.K, a.V, a.d,
-                      walk_agg_active(n_walks, a.L, a.R, a.K, a.d, exact), base, p, st);
+    return plan_walks(ar, n_walks, a.L, a.R, a.K, a.V, a.d,
+                      walk_agg_active(n_walks, a.L, a.R, a.K, a.d, exact), p, st);
 }
 
 int launch_walk_agg(const SgnsArgs &a, const WalkPlan &p, hipStream_t st) {
@@ -2141,22 +2055,22 @@ int launch_sgns_impl(SgnsArgs a, void *workspace, size_t workspace_bytes, int ph
     DW_REQUIRE(a.V <= 0x7FFFFFFF, "dw_sgns: records mode needs vocab_size < 2^31");
     DW_REQUIRE(a.batch * T < 0x7FFFFFFF, "dw_sgns: records mode needs batch*2R(1+K) < 2^31");
     WalkPlan plan;
+    Arena ar{static_cast<char *>(workspace)};
     int rc;
     if constexpr (FROM_WALKS) {
-        rc = plan_walks_for(a, workspace, &plan, st);
+        rc = plan_walks_for(a, ar, &plan, st);
     } else {   // pairs: one record per (centre, slot)
         plan.agg = false;
         plan.n_neg = 0;
         plan.n_rec = a.batch * T;
         plan.coef_pos = plan.agg_rows = nullptr;
-        rc = plan_workspace(plan.n_rec, a.V, workspace, &plan.ws, st);
-        plan.total = plan.ws.total;
+        rc = plan_workspace(ar, plan.n_rec, a.V, &plan.ws, st);
     }
     if (rc != DW_OK) return rc;
     const Workspace &ws = plan.ws;
     const int64_t n_rec = plan.n_rec;
-    DW_REQUIRE(workspace_bytes >= plan.total, "dw_sgns: workspace too small (%zu < %zu)%s",
-               workspace_bytes, plan.total,
+    DW_REQUIRE(workspace_bytes >= ar.off, "dw_sgns: workspace too small (%zu < %zu)%s",
+               workspace_bytes, ar.off,
                plan.agg ? " (walk aggregation: size it with dw_sgns_walks_workspace_bytes)" : "");
     if (do1) {
         a.rec_key = ws.k0;
@@ -2174,9 +2088,8 @@ int launch_sgns_impl(SgnsArgs a, void *workspace, size_t workspace_bytes, int ph
             if (rc != DW_OK) return rc;
         }
         if (a.fx_in.acc && !(fl & (DW_EXACT_DEFER | DW_EXACT_ADAM))) {   // the centres' exact
-            int64_t cb = (a.batch + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-            if (cb > grid_cap(8)) cb = grid_cap(8);
-            hipLaunchKernelGGL(k_fixed_centres<FROM_WALKS>, dim3((unsigned)cb),
+            hipLaunchKernelGGL(k_fixed_centres<FROM_WALKS>,
+                               dim3(grid_for(a.batch, WAVES_PER_BLOCK, 0, grid_cap(8))),
                                dim3(WAVES_PER_BLOCK * WAVE), 0, st, a);
             DW_LAUNCH_CHECK("dw_sgns/fixed_centres");
         }
@@ -2235,12 +2148,13 @@ int launch_pieces(SgnsArgs a, void *workspace, size_t workspace_bytes, int piece
     DW_REQUIRE(T <= TMAX && a.V <= 0x7FFFFFFF, "dw_sgns_walks_phase2_piece: records mode limits");
     DW_REQUIRE(a.batch * T < 0x7FFFFFFF, "dw_sgns_walks_phase2_piece: too many records");
     WalkPlan plan;   // the preceding phase-1 call's (the same arguments)
-    int rc = plan_walks_for(a, workspace, &plan, st);
+    Arena ar{static_cast<char *>(workspace)};
+    int rc = plan_walks_for(a, ar, &plan, st);
     if (rc != DW_OK) return rc;
     const Workspace &ws = plan.ws;
     const int64_t n_rec = a.batch > 0 ? plan.n_rec : 0;
-    DW_REQUIRE(workspace_bytes >= plan.total, "dw_sgns: workspace too small (%zu < %zu)",
-               workspace_bytes, plan.total);
+    DW_REQUIRE(workspace_bytes >= ar.off, "dw_sgns: workspace too small (%zu < %zu)",
+               workspace_bytes, ar.off);
     if (piece == -1) {
         bool in_k1 = false;
         if (n_rec > 0) {
@@ -2297,9 +2211,7 @@ struct OwnerLayout {
 
 OwnerLayout owner_layout(int64_t n_centres, int64_t T) {
     OwnerLayout l;
-    l.blocks = (n_centres + 4 * WAVES_PER_BLOCK - 1) / (4 * WAVES_PER_BLOCK);  // = launch_pass1_g16
-    if (l.blocks > grid_cap(8)) l.blocks = grid_cap(8);
-    if (l.blocks < 1) l.blocks = 1;
+    l.blocks = grid_for(n_centres, 4 * WAVES_PER_BLOCK, 1, grid_cap(8));  // = launch_pass1_g16
     l.n_waves = l.blocks * WAVES_PER_BLOCK;
     const int64_t per_sweep = l.n_waves * 4;  // centres per grid-stride iteration
     const int64_t iters = (n_centres + per_sweep - 1) / per_sweep;
@@ -2446,11 +2358,11 @@ __global__ void __launch_bounds__(OCC_SMALL_THREADS)
 // the owner form's tail of the workspace (after the records part): the occurrence sort
 struct OccSpace {
     uint32_t *k0, *k1, *v0, *v1;
-    void *tmp;
-    size_t tmp_bytes, total;
+    char *tmp;   // the sort's and the unique step's temporary storage (the larger need)
+    size_t tmp_bytes;
 };
 
-int plan_occ(int64_t n_centres, int64_t V, void *base, OccSpace *o, hipStream_t st) {
+int plan_occ(Arena &a, int64_t n_centres, int64_t V, OccSpace *o, hipStream_t st) {
     size_t tmp = 0, utmp = 0;
     rocprim::double_buffer<uint32_t> kb(nullptr, nullptr), vb(nullptr, nullptr);
     if (sort_pairs(nullptr, tmp, kb, vb, static_cast<uint32_t>(n_centres), end_bit_for(V),
@@ -2462,41 +2374,28 @@ int plan_occ(int64_t n_centres, int64_t V, void *base, OccSpace *o, hipStream_t 
         dw::set_error("dw_sgns_owner: occurrence sort / unique size query failed");
         return DW_E_HIP;
     }
-    if (utmp > tmp) tmp = utmp;
-    const size_t a = align256((size_t)n_centres * 4);
-    char *p = static_cast<char *>(base);
-    o->k0 = reinterpret_cast<uint32_t *>(p);
-    o->k1 = reinterpret_cast<uint32_t *>(p + a);
-    o->v0 = reinterpret_cast<uint32_t *>(p + 2 * a);
-    o->v1 = reinterpret_cast<uint32_t *>(p + 3 * a);
-    o->tmp = p + 4 * a;
-    o->tmp_bytes = tmp;
-    o->total = 4 * a + align256(tmp);
+    o->tmp_bytes = utmp > tmp ? utmp : tmp;
+    o->k0 = a.take<uint32_t>(n_centres);
+    o->k1 = a.take<uint32_t>(n_centres);
+    o->v0 = a.take<uint32_t>(n_centres);
+    o->v1 = a.take<uint32_t>(n_centres);
+    o->tmp = a.take<char>(o->tmp_bytes);
     return DW_OK;
 }
 
 // the records' placement (k_out_claim's ranks, one owner or many): rank[slot], off[row] (the
 // exclusive scan of the per-row counts, with one zero past the rows: off[local_rows] = their
-// total) and the scan's temporary storage; between the records part and OccSpace
+// total) and the scan's per-tile sums; between the records part and OccSpace
 constexpr int PLACE_TILE = 4096;   // placement-scan counts per block (16 per thread; k_place_scan)
 
 struct PlaceSpace {
-    uint32_t *rank, *off;
-    void *tmp;
-    size_t tmp_bytes, total;
+    uint32_t *rank, *off, *sums;
 };
 
-int plan_place(int64_t n_slots, int64_t local_rows, void *base, PlaceSpace *pl, hipStream_t st) {
-    (void)st;
-    const size_t tmp = static_cast<size_t>((local_rows + PLACE_TILE - 1) / PLACE_TILE) * 4;
-    const size_t a = align256((size_t)(n_slots > 0 ? n_slots : 1) * 4);
-    const size_t b = align256((size_t)(local_rows + 1) * 4);
-    char *p = static_cast<char *>(base);
-    pl->rank = reinterpret_cast<uint32_t *>(p);
-    pl->off = reinterpret_cast<uint32_t *>(p + a);
-    pl->tmp = p + a + b;
-    pl->tmp_bytes = tmp;
-    pl->total = a + b + align256(tmp);
+int plan_place(Arena &a, int64_t n_slots, int64_t local_rows, PlaceSpace *pl) {
+    pl->rank = a.take<uint32_t>(n_slots > 0 ? n_slots : 1);
+    pl->off = a.take<uint32_t>(local_rows + 1);
+    pl->sums = a.take<uint32_t>((local_rows + PLACE_TILE - 1) / PLACE_TILE);
     return DW_OK;
 }
 
@@ -2510,21 +2409,14 @@ int owner_workspace(int64_t n_centres, int64_t T, int64_t local_rows, void *work
     DW_REQUIRE(lay->n_waves <= MAX_OWNER_WAVES, "%s: %lld pass-1 waves > %d", what,
                (long long)lay->n_waves, MAX_OWNER_WAVES);
     DW_REQUIRE(workspace != nullptr, "%s: needs the records workspace", what);
-    int rc = plan_workspace(lay->total, local_rows, workspace, ws, st);
-    if (rc != DW_OK) return rc;
+    Arena a{static_cast<char *>(workspace)};   // records, placement, then the occurrence space
     PlaceSpace pl;
-    rc = plan_place(n_centres * T, local_rows, static_cast<char *>(workspace) + ws->total, &pl, st);
+    int rc = plan_workspace(a, lay->total, local_rows, ws, st);
+    if (rc == DW_OK) rc = plan_place(a, n_centres * T, local_rows, place ? place : &pl);
+    if (rc == DW_OK && occ) rc = plan_occ(a, n_centres > 0 ? n_centres : 1, V, occ, st);
     if (rc != DW_OK) return rc;
-    if (place) *place = pl;
-    size_t need = ws->total + pl.total;
-    if (occ) {
-        rc = plan_occ(n_centres > 0 ? n_centres : 1, V, static_cast<char *>(workspace) + need, occ,
-                      st);
-        if (rc != DW_OK) return rc;
-        need += occ->total;
-    }
-    DW_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%zu < %zu)", what,
-               workspace_bytes, need);
+    DW_REQUIRE(workspace_bytes >= a.off, "%s: workspace too small (%zu < %zu)", what,
+               workspace_bytes, a.off);
     return DW_OK;
 }
 
@@ -2539,10 +2431,8 @@ int owner_order(const SgnsArgs &a, const OccSpace &occ, uint32_t *touched, int64
         DW_LAUNCH_CHECK("dw_sgns_owner/occ_small");
         return DW_OK;
     }
-    int64_t ob = (a.batch + 255) / 256;
-    if (ob > grid_cap(8)) ob = grid_cap(8);
-    hipLaunchKernelGGL(k_occ_keys, dim3((unsigned)ob), dim3(256), 0, st, a.walks, a.batch, a.L,
-                       a.R, occ.k0, occ.v0);
+    hipLaunchKernelGGL(k_occ_keys, dim3(grid_for(a.batch, 256, 0, grid_cap(8))), dim3(256), 0, st,
+                       a.walks, a.batch, a.L, a.R, occ.k0, occ.v0);
     DW_LAUNCH_CHECK("dw_sgns_owner/occ_keys");
     rocprim::double_buffer<uint32_t> kb(occ.k0, occ.k1), vb(occ.v0, occ.v1);
     size_t tb = occ.tmp_bytes;
@@ -2649,9 +2539,8 @@ int launch_owner_pass1(SgnsArgs a, int64_t local_rows, int32_t order_ready, void
                     : launch_pass1_g16<true, true>(a, st);
         if (rc != DW_OK) return rc;
         if (a.fx_in.acc && !(fl & (DW_EXACT_DEFER | DW_EXACT_ADAM))) {   // one rank: the centres' exact sums
-            int64_t cb = (a.batch + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-            if (cb > grid_cap(8)) cb = grid_cap(8);
-            hipLaunchKernelGGL(k_fixed_centres<true>, dim3((unsigned)cb),
+            hipLaunchKernelGGL(k_fixed_centres<true>,
+                               dim3(grid_for(a.batch, WAVES_PER_BLOCK, 0, grid_cap(8))),
                                dim3(WAVES_PER_BLOCK * WAVE), 0, st, a);
             DW_LAUNCH_CHECK("dw_sgns_owner_pass1/fixed_centres");
         }
@@ -2659,9 +2548,8 @@ int launch_owner_pass1(SgnsArgs a, int64_t local_rows, int32_t order_ready, void
             hipLaunchKernelGGL(k_wave_scan, dim3(1), dim3(1024), 0, st, ws.wave_counts,
                                lay.n_waves, ws.wave_offsets, ws.count);
             DW_LAUNCH_CHECK("dw_sgns_owner_pass1/scan");
-            int64_t cb = lay.n_waves < 65536 ? lay.n_waves : 65536;
-            hipLaunchKernelGGL(k_rec_compact, dim3((unsigned)cb), dim3(256), 0, st,
-                               ws.wave_counts, ws.wave_offsets, lay.n_waves, lay.region, ws.k0,
+            hipLaunchKernelGGL(k_rec_compact, dim3(grid_for(lay.n_waves, 1, 0, 65536)), dim3(256),
+                               0, st, ws.wave_counts, ws.wave_offsets, lay.n_waves, lay.region, ws.k0,
                                ws.v0, ws.k1, ws.v1);
             DW_LAUNCH_CHECK("dw_sgns_owner_pass1/compact");
         }
@@ -2710,10 +2598,8 @@ int launch_owner_pass2(int64_t n_centres, int64_t T, int64_t local_rows, int32_t
         *n_records = n_rec;
     } else if (bound > 0) {
         // no readback: sort the bound with the tail padded, gather [0, count) (k_rec_pad)
-        int64_t pb = (bound + 255) / 256;
-        if (pb > grid_cap(4)) pb = grid_cap(4);
-        hipLaunchKernelGGL(k_rec_pad, dim3((unsigned)pb), dim3(256), 0, st, ws.count, bound,
-                           ws.k1, ws.v1, ws.bounds);
+        hipLaunchKernelGGL(k_rec_pad, dim3(grid_for(bound, 256, 0, grid_cap(4))), dim3(256), 0, st,
+                           ws.count, bound, ws.k1, ws.v1, ws.bounds);
         DW_LAUNCH_CHECK("dw_sgns_owner_pass2/pad");
         range = ws.bounds;
     }
@@ -2862,6 +2748,28 @@ __global__ void __launch_bounds__(256)
 
 using RenormSortConfig = RecordSortConfig;
 
+// dw_embedding_renorm's workspace: the ids as sort keys, double-buffered, and the sort's storage
+struct RenormBufs {
+    uint32_t *k0, *k1;
+    char *tmp;
+    size_t tmp_bytes;
+};
+
+int plan_renorm(Arena &a, int64_t n_ids, int64_t V, RenormBufs *p) {
+    rocprim::double_buffer<uint32_t> kb(nullptr, nullptr);
+    hipError_t e = rocprim::radix_sort_keys<RenormSortConfig>(
+        nullptr, p->tmp_bytes, kb, static_cast<uint32_t>(n_ids > 0 ? n_ids : 1), 0,
+        end_bit_for(V + 1), nullptr);
+    if (e != hipSuccess) {
+        dw::set_error("dw_embedding_renorm: sort size query failed: %s", hipGetErrorString(e));
+        return DW_E_HIP;
+    }
+    p->k0 = a.take<uint32_t>(n_ids);
+    p->k1 = a.take<uint32_t>(n_ids);
+    p->tmp = a.take<char>(p->tmp_bytes);
+    return DW_OK;
+}
+
 SgnsArgs base_args(int64_t V, int32_t dim, int32_t K, const float *w_in, const float *w_out,
                    float *g_in, float *g_out, const int64_t *noise, uint64_t seed,
                    uint64_t noise_offset, float grad_scale, double *loss_acc, int32_t *status) {
@@ -2883,6 +2791,42 @@ SgnsArgs base_args(int64_t V, int32_t dim, int32_t K, const float *w_in, const f
     a.status = status;
     a.dyn = dw::bound_step_scalars();
     return a;
+}
+
+// The shape of a walks call, stated once: n_walks walks of L positions give n_walks (L - 2R)
+// centres of C = 2R contexts, T = 2R(1+K) output rows each. Refuses a bad shape under the
+// caller's name (`rest`: the caller's other size conditions, part of the same message) and
+// fills the walks fields of `a` when there is one.
+struct WalkShape {
+    int64_t n_centres, T;
+};
+
+int walk_shape(const char *who, const int32_t *walks, int64_t n_walks, int32_t L, int32_t R,
+               int32_t K, bool rest, WalkShape *s, SgnsArgs *a = nullptr) {
+    DW_REQUIRE(R >= 1 && L >= 2 * R + 1 && n_walks >= 0 && K >= 0 && rest, "%s: bad sizes", who);
+    s->n_centres = n_walks * (L - 2 * R);
+    s->T = 2 * (int64_t)R * (1 + (int64_t)K);
+    if (a) {
+        a->walks = walks;
+        a->L = L;
+        a->R = R;
+        a->batch = s->n_centres;
+        a->C = 2 * R;
+    }
+    return DW_OK;
+}
+
+// The fused output-table Adam of one step from its seven host scalars (float64 on the host, cast
+// to float32), or the bound step block's when there is one.
+OutAdam fused_adam(float *p, float *m, float *v, uint8_t *flags, float one_minus_beta1,
+                   float beta2, float one_minus_beta2, float bias_correction2_sqrt,
+                   float neg_step_size, float eps, float weight_decay) {
+    OutAdam oa{p, m, v, flags,
+               dw::AdamScalars{one_minus_beta1, beta2, one_minus_beta2, bias_correction2_sqrt,
+                               neg_step_size, eps, weight_decay,
+                               bias_correction2_sqrt > 0.f ? 1.0f / bias_correction2_sqrt : 0.f}};
+    oa.dyn = dw::bound_step_scalars();
+    return oa;
 }
 
 // Lazy out slice (dw_sgns_owner_out_catch_up), before pass 1: every owned output row a slot of
@@ -3140,12 +3084,17 @@ int dw_sgns_owner_out_catch_up(const int32_t *walks, int64_t n_walks, int32_t wa
                                uint32_t *rows_buf, int64_t *n_rows, const float *hist,
                                int32_t step, int32_t flags, int32_t *status, void *workspace,
                                size_t workspace_bytes, void *stream) {
-    DW_REQUIRE(context_radius >= 1 && walk_length >= 2 * context_radius + 1 && n_walks >= 0 &&
-                   dim >= 1 && vocab_size >= 1 && neg_samples >= 0 && n_owners >= 1 &&
-                   owner >= 0 && owner < n_owners && step >= 1,
-               "dw_sgns_owner_out_catch_up: bad sizes");
-    DW_REQUIRE(2 * (int64_t)context_radius * (1 + neg_samples) <= WAVE,
-               "dw_sgns_owner_out_catch_up: 2R(1+K) must be <= 64");
+    SgnsArgs a = base_args(vocab_size, dim, neg_samples, nullptr, w_out_local, nullptr, nullptr,
+                           noise, seed, noise_offset, 0.f, nullptr, status);
+    WalkShape sh;
+    int rc = walk_shape("dw_sgns_owner_out_catch_up", walks, n_walks, walk_length, context_radius,
+                        neg_samples,
+                        dim >= 1 && vocab_size >= 1 && n_owners >= 1 && owner >= 0 &&
+                            owner < n_owners && step >= 1,
+                        &sh, &a);
+    if (rc != DW_OK) return rc;
+    const int64_t T = sh.T;
+    DW_REQUIRE(T <= WAVE, "dw_sgns_owner_out_catch_up: 2R(1+K) must be <= 64");
     DW_REQUIRE(local_rows * n_owners >= vocab_size,
                "dw_sgns_owner_out_catch_up: the owners' rows do not cover the vocabulary");
     if (n_walks == 0) return DW_OK;
@@ -3161,22 +3110,14 @@ int dw_sgns_owner_out_catch_up(const int32_t *walks, int64_t n_walks, int32_t wa
     hipStream_t st = dw::as_stream(stream);
     const dw_step_scalars *dyn = nullptr;
     int32_t delta = 0;
-    int rc = dw::bound_step_rel(step, &dyn, &delta, "dw_sgns_owner_out_catch_up");
+    rc = dw::bound_step_rel(step, &dyn, &delta, "dw_sgns_owner_out_catch_up");
     if (rc != DW_OK) return rc;
-    SgnsArgs a = base_args(vocab_size, dim, neg_samples, nullptr, w_out_local, nullptr, nullptr,
-                           noise, seed, noise_offset, 0.f, nullptr, status);
-    a.walks = walks;
-    a.L = walk_length;
-    a.R = context_radius;
-    a.batch = n_walks * (walk_length - 2 * context_radius);
-    a.C = 2 * context_radius;
     a.owner = owner;
     a.n_owners = n_owners;
     if (!(flags & 4) && hipMemsetAsync(n_rows, 0, sizeof(int64_t), st) != hipSuccess) {
         dw::set_error("dw_sgns_owner_out_catch_up: counter reset failed");
         return DW_E_HIP;
     }
-    const int64_t T = (int64_t)a.C * (1 + a.K);
     Workspace ws;
     OwnerLayout lay;
     PlaceSpace pl{};
@@ -3186,36 +3127,30 @@ int dw_sgns_owner_out_catch_up(const int32_t *walks, int64_t n_walks, int32_t wa
         if (rc != DW_OK) return rc;
     }
     const int64_t ctile = (int64_t)WAVES_PER_BLOCK * (rows_major ? 1 : CLAIM_TRIPS);
-    int64_t blocks = (a.batch + ctile - 1) / ctile;
-    if (blocks > grid_cap(8)) blocks = grid_cap(8);
-    if (blocks < 1) blocks = 1;
+    const dim3 g(grid_for(a.batch, ctile, 1, grid_cap(8)));
     // (rows-major: every slot's row into the records' spare key buffer, k0)
     if (rows_major)
-        hipLaunchKernelGGL(k_out_claim<false>, dim3((unsigned)blocks),
-                           dim3(WAVES_PER_BLOCK * WAVE), 0, st, a, claim, step, delta, rows_buf,
+        hipLaunchKernelGGL(k_out_claim<false>, g, dim3(WAVES_PER_BLOCK * WAVE), 0, st, a, claim,
+                           step, delta, rows_buf,
                            reinterpret_cast<unsigned long long *>(n_rows), counts, pl.rank,
                            ws.k0);
     else
-        hipLaunchKernelGGL(k_out_claim<true>, dim3((unsigned)blocks),
-                           dim3(WAVES_PER_BLOCK * WAVE), 0, st, a, claim, step, delta, rows_buf,
+        hipLaunchKernelGGL(k_out_claim<true>, g, dim3(WAVES_PER_BLOCK * WAVE), 0, st, a, claim,
+                           step, delta, rows_buf,
                            reinterpret_cast<unsigned long long *>(n_rows),
                            place ? counts : nullptr, place ? pl.rank : nullptr, nullptr);
     DW_LAUNCH_CHECK("dw_sgns_owner_out_catch_up/claim");
     if (place) {   // every row's segment of the records: the scan of the counts (+ the total)
-        const int64_t nb = (local_rows + PLACE_TILE - 1) / PLACE_TILE;
-        DW_REQUIRE(pl.tmp_bytes >= (size_t)nb * 4, "dw_sgns_owner_out_catch_up: scan scratch");
-        uint32_t *sums = static_cast<uint32_t *>(pl.tmp);
+        const int64_t nb = (local_rows + PLACE_TILE - 1) / PLACE_TILE;   // = plan_place's sums
         hipLaunchKernelGGL(k_place_sums, dim3((unsigned)nb), dim3(256), 0, st, counts, local_rows,
-                           sums);
+                           pl.sums);
         hipLaunchKernelGGL(k_place_scan, dim3((unsigned)nb), dim3(256), 0, st, counts, local_rows,
-                           sums, pl.off, ws.bounds);
+                           pl.sums, pl.off, ws.bounds);
         DW_LAUNCH_CHECK("dw_sgns_owner_out_catch_up/place");
     }
     if (rows_major) {   // the slots into their rows' segments; no catch-up
-        int64_t pb = (a.batch * T + 255) / 256;
-        if (pb > grid_cap(8)) pb = grid_cap(8);
-        if (pb < 1) pb = 1;
-        hipLaunchKernelGGL(k_place_slots, dim3((unsigned)pb), dim3(256), 0, st, a.batch * T,
+        hipLaunchKernelGGL(k_place_slots, dim3(grid_for(a.batch * T, 256, 1, grid_cap(8))),
+                           dim3(256), 0, st, a.batch * T,
                            ws.k0, pl.rank, pl.off, ws.k1, ws.v1, walks, walk_length,
                            context_radius, static_cast<int32_t>(T), 1 + neg_samples);
         DW_LAUNCH_CHECK("dw_sgns_owner_out_catch_up/place_slots");
@@ -3260,10 +3195,8 @@ int dw_fixed_to_float(int64_t *acc, float *grad, int64_t n, int32_t frac, int32_
     DW_REQUIRE(n >= 0 && frac >= 0 && frac <= 62, "dw_fixed_to_float: bad arguments");
     if (n == 0) return DW_OK;
     DW_REQUIRE(acc && grad, "dw_fixed_to_float: null pointer");
-    int64_t blocks = (n + 255) / 256;
-    if (blocks > grid_cap(8)) blocks = grid_cap(8);
-    hipLaunchKernelGGL(k_fixed_dense, dim3((unsigned)blocks), dim3(256), 0, dw::as_stream(stream),
-                       acc, grad, n, ldexp(1.0, -frac), accumulate);
+    hipLaunchKernelGGL(k_fixed_dense, dim3(grid_for(n, 256, 0, grid_cap(8))), dim3(256), 0,
+                       dw::as_stream(stream), acc, grad, n, ldexp(1.0, -frac), accumulate);
     DW_LAUNCH_CHECK("dw_fixed_to_float");
     return DW_OK;
 }
@@ -3303,10 +3236,10 @@ int dw_sgns_workspace_bytes(int64_t n_centres, int32_t n_ctx, int32_t neg_sample
     const int64_t n_rec = n_centres * n_ctx * (1 + (int64_t)neg_samples);
     DW_REQUIRE(n_rec < 0x7FFFFFFF, "dw_sgns_workspace_bytes: too many records");
     Workspace ws;
-    char dummy;
-    int rc = plan_workspace(n_rec > 0 ? n_rec : 1, vocab_size, &dummy, &ws, nullptr);
+    Arena a{nullptr};
+    const int rc = plan_workspace(a, n_rec > 0 ? n_rec : 1, vocab_size, &ws, nullptr);
     if (rc != DW_OK) return rc;
-    *bytes = ws.total;
+    *bytes = a.off;
     return DW_OK;
 }
 
@@ -3314,26 +3247,22 @@ int dw_sgns_walks_workspace_bytes(int64_t n_walks, int32_t walk_length, int32_t 
                                   int32_t neg_samples, int64_t vocab_size, int32_t dim,
                                   size_t *bytes) {
     DW_REQUIRE(bytes, "dw_sgns_walks_workspace_bytes: bytes is null");
-    DW_REQUIRE(n_walks >= 0 && context_radius >= 1 && walk_length >= 2 * context_radius + 1 &&
-                   neg_samples >= 0 && vocab_size >= 1 && dim >= 1,
-               "dw_sgns_walks_workspace_bytes: bad sizes");
-    const int64_t n_rec = n_walks * (walk_length - 2 * context_radius) * 2 * context_radius *
-                          (1 + (int64_t)neg_samples);
-    DW_REQUIRE(n_rec < 0x7FFFFFFF, "dw_sgns_walks_workspace_bytes: too many records");
-    WalkPlan p;
-    char dummy;
-    int rc = plan_walks(n_walks, walk_length, context_radius, neg_samples, vocab_size, dim, false,
-                        &dummy, &p, nullptr);
+    WalkShape sh;
+    int rc = walk_shape("dw_sgns_walks_workspace_bytes", nullptr, n_walks, walk_length,
+                        context_radius, neg_samples, vocab_size >= 1 && dim >= 1, &sh);
     if (rc != DW_OK) return rc;
-    size_t need = p.total;
+    DW_REQUIRE(sh.n_centres * sh.T < 0x7FFFFFFF,
+               "dw_sgns_walks_workspace_bytes: too many records");
+    WalkPlan p;
+    Arena legacy{nullptr}, agg{nullptr};
+    rc = plan_walks(legacy, n_walks, walk_length, context_radius, neg_samples, vocab_size, dim,
+                    false, &p, nullptr);
     // whatever dw_sgns_set_walk_agg says at the calls: the larger of the two layouts
-    if (walk_agg_shape_ok(n_walks, walk_length, context_radius, neg_samples, dim)) {
-        rc = plan_walks(n_walks, walk_length, context_radius, neg_samples, vocab_size, dim, true,
-                        &dummy, &p, nullptr);
-        if (rc != DW_OK) return rc;
-        need = p.total > need ? p.total : need;
-    }
-    *bytes = need;
+    if (rc == DW_OK && walk_agg_shape_ok(n_walks, walk_length, context_radius, neg_samples, dim))
+        rc = plan_walks(agg, n_walks, walk_length, context_radius, neg_samples, vocab_size, dim,
+                        true, &p, nullptr);
+    if (rc != DW_OK) return rc;
+    *bytes = agg.off > legacy.off ? agg.off : legacy.off;
     return DW_OK;
 }
 
@@ -3345,9 +3274,10 @@ int dw_sgns_set_walk_agg(int32_t mode) {
 
 int dw_sgns_walk_agg_active(int64_t n_walks, int32_t walk_length, int32_t context_radius,
                             int32_t neg_samples, int32_t dim) {
-    DW_REQUIRE(n_walks >= 0 && context_radius >= 1 && walk_length >= 2 * context_radius + 1 &&
-                   neg_samples >= 0 && dim >= 1,
-               "dw_sgns_walk_agg_active: bad sizes");
+    WalkShape sh;
+    const int rc = walk_shape("dw_sgns_walk_agg_active", nullptr, n_walks, walk_length,
+                              context_radius, neg_samples, dim >= 1, &sh);
+    if (rc != DW_OK) return rc;
     return walk_agg_active(n_walks, walk_length, context_radius, neg_samples, dim, false) ? 1 : 0;
 }
 
@@ -3359,19 +3289,15 @@ int sgns_walks(int phase, const int32_t *walks, int64_t n_walks, int32_t walk_le
                double *loss_acc, int32_t *status, void *workspace, size_t workspace_bytes,
                void *stream) {
     DW_REQUIRE(phase >= 0 && phase <= 2, "dw_sgns_walks_phase: phase must be 0, 1 or 2");
-    DW_REQUIRE(context_radius >= 1, "dw_sgns_walks: context_radius must be >= 1");
-    DW_REQUIRE(walk_length >= 2 * context_radius + 1,
-               "dw_sgns_walks: walk_length %d < 2R+1 (Text is too short!)", walk_length);
-    DW_REQUIRE(neg_samples >= 0 && dim >= 1 && vocab_size >= 1 && n_walks >= 0,
-               "dw_sgns_walks: bad sizes");
-    DW_REQUIRE(walks && w_in && w_out && g_in && g_out && status, "dw_sgns_walks: null pointer");
+    int rc = dw::require_window("dw_sgns_walks", walk_length, context_radius);
+    if (rc != DW_OK) return rc;
     SgnsArgs a = base_args(vocab_size, dim, neg_samples, w_in, w_out, g_in, g_out, noise, seed,
                            noise_offset, grad_scale, loss_acc, status);
-    a.walks = walks;
-    a.L = walk_length;
-    a.R = context_radius;
-    a.batch = n_walks * (walk_length - 2 * context_radius);
-    a.C = 2 * context_radius;
+    WalkShape sh;
+    rc = walk_shape("dw_sgns_walks", walks, n_walks, walk_length, context_radius, neg_samples,
+                    dim >= 1 && vocab_size >= 1, &sh, &a);
+    if (rc != DW_OK) return rc;
+    DW_REQUIRE(walks && w_in && w_out && g_in && g_out && status, "dw_sgns_walks: null pointer");
     return launch_sgns<true>(a, workspace, workspace_bytes, phase, dw::as_stream(stream));
 }
 }  // namespace
@@ -3398,22 +3324,16 @@ int dw_sgns_walks_phase2_adam(const int32_t *walks, int64_t n_walks, int32_t wal
     DW_REQUIRE(workspace && m_out && v_out && row_flags && w_out && g_out,
                "dw_sgns_walks_phase2_adam: needs the records workspace and the Adam state");
     DW_REQUIRE(bias_correction2_sqrt > 0.f, "dw_sgns_walks_phase2_adam: bad Adam scalars");
-    DW_REQUIRE(context_radius >= 1 && walk_length >= 2 * context_radius + 1 && n_walks >= 0 &&
-                   dim >= 1 && vocab_size >= 1 && neg_samples >= 0,
-               "dw_sgns_walks_phase2_adam: bad sizes");
-    DW_REQUIRE(walks && w_in && status, "dw_sgns_walks_phase2_adam: null pointer");
     SgnsArgs a = base_args(vocab_size, dim, neg_samples, w_in, w_out, nullptr, g_out, nullptr,
                            0, 0, 1.f, nullptr, status);
-    a.walks = walks;
-    a.L = walk_length;
-    a.R = context_radius;
-    a.batch = n_walks * (walk_length - 2 * context_radius);
-    a.C = 2 * context_radius;
-    OutAdam oa{w_out, m_out, v_out, row_flags,
-               dw::AdamScalars{one_minus_beta1, beta2, one_minus_beta2, bias_correction2_sqrt,
-                               neg_step_size, eps, weight_decay,
-                               bias_correction2_sqrt > 0.f ? 1.0f / bias_correction2_sqrt : 0.f}};
-    oa.dyn = dw::bound_step_scalars();
+    WalkShape sh;
+    const int rc = walk_shape("dw_sgns_walks_phase2_adam", walks, n_walks, walk_length,
+                              context_radius, neg_samples, dim >= 1 && vocab_size >= 1, &sh, &a);
+    if (rc != DW_OK) return rc;
+    DW_REQUIRE(walks && w_in && status, "dw_sgns_walks_phase2_adam: null pointer");
+    const OutAdam oa = fused_adam(w_out, m_out, v_out, row_flags, one_minus_beta1, beta2,
+                                  one_minus_beta2, bias_correction2_sqrt, neg_step_size, eps,
+                                  weight_decay);
     return launch_sgns<true>(a, workspace, workspace_bytes, 2, dw::as_stream(stream), &oa);
 }
 
@@ -3422,17 +3342,13 @@ int dw_sgns_walks_phase2_piece(int32_t piece, int32_t n_pieces, int64_t piece_ro
                                int32_t context_radius, int32_t neg_samples, int64_t vocab_size,
                                int32_t dim, const float *w_in, float *g_out, int32_t *status,
                                void *workspace, size_t workspace_bytes, void *stream) {
-    DW_REQUIRE(context_radius >= 1 && walk_length >= 2 * context_radius + 1 && n_walks >= 0 &&
-                   dim >= 1 && vocab_size >= 1 && neg_samples >= 0,
-               "dw_sgns_walks_phase2_piece: bad sizes");
-    DW_REQUIRE(walks && w_in && g_out && status, "dw_sgns_walks_phase2_piece: null pointer");
     SgnsArgs a = base_args(vocab_size, dim, neg_samples, w_in, nullptr, nullptr, g_out, nullptr,
                            0, 0, 1.f, nullptr, status);
-    a.walks = walks;
-    a.L = walk_length;
-    a.R = context_radius;
-    a.batch = n_walks * (walk_length - 2 * context_radius);
-    a.C = 2 * context_radius;
+    WalkShape sh;
+    const int rc = walk_shape("dw_sgns_walks_phase2_piece", walks, n_walks, walk_length,
+                              context_radius, neg_samples, dim >= 1 && vocab_size >= 1, &sh, &a);
+    if (rc != DW_OK) return rc;
+    DW_REQUIRE(walks && w_in && g_out && status, "dw_sgns_walks_phase2_piece: null pointer");
     return launch_pieces(a, workspace, workspace_bytes, piece, n_pieces, piece_rows,
                          dw::as_stream(stream));
 }
@@ -3460,15 +3376,13 @@ int dw_sgns_owner_workspace_bytes(int64_t n_centres, int32_t n_ctx, int32_t neg_
     Workspace ws;
     OccSpace occ;
     PlaceSpace pl;
-    char dummy;
-    int rc = plan_workspace(lay.total > 0 ? lay.total : 1, local_rows, &dummy, &ws, nullptr);
+    Arena a{nullptr};   // owner_workspace's sequence, every part present
+    int rc = plan_workspace(a, lay.total > 0 ? lay.total : 1, local_rows, &ws, nullptr);
+    if (rc == DW_OK)
+        rc = plan_place(a, n_centres * (int64_t)n_ctx * (1 + neg_samples), local_rows, &pl);
+    if (rc == DW_OK) rc = plan_occ(a, n_centres > 0 ? n_centres : 1, vocab_size, &occ, nullptr);
     if (rc != DW_OK) return rc;
-    rc = plan_place(n_centres * (int64_t)n_ctx * (1 + neg_samples), local_rows, &dummy, &pl,
-                    nullptr);
-    if (rc != DW_OK) return rc;
-    rc = plan_occ(n_centres > 0 ? n_centres : 1, vocab_size, &dummy, &occ, nullptr);
-    if (rc != DW_OK) return rc;
-    *bytes = ws.total + pl.total + occ.total;
+    *bytes = a.off;
     return DW_OK;
 }
 
@@ -3476,18 +3390,14 @@ int dw_sgns_owner_prepare(const int32_t *walks, int64_t n_walks, int32_t walk_le
                           int32_t context_radius, int32_t neg_samples, int64_t vocab_size,
                           int64_t local_rows, uint32_t *touched, int64_t *n_touched,
                           void *workspace, size_t workspace_bytes, void *stream) {
-    DW_REQUIRE(context_radius >= 1 && walk_length >= 2 * context_radius + 1 && n_walks >= 0 &&
-                   vocab_size >= 1 && local_rows >= 1 && neg_samples >= 0,
-               "dw_sgns_owner_prepare: bad sizes");
-    DW_REQUIRE((walks || n_walks == 0) && (!touched || n_touched),
-               "dw_sgns_owner_prepare: null pointer");
     SgnsArgs a = base_args(vocab_size, 64, neg_samples, nullptr, nullptr, nullptr, nullptr,
                            nullptr, 0, 0, 1.f, nullptr, nullptr);
-    a.walks = walks;
-    a.L = walk_length;
-    a.R = context_radius;
-    a.batch = n_walks * (walk_length - 2 * context_radius);
-    a.C = 2 * context_radius;
+    WalkShape sh;
+    const int rc = walk_shape("dw_sgns_owner_prepare", walks, n_walks, walk_length, context_radius,
+                              neg_samples, vocab_size >= 1 && local_rows >= 1, &sh, &a);
+    if (rc != DW_OK) return rc;
+    DW_REQUIRE((walks || n_walks == 0) && (!touched || n_touched),
+               "dw_sgns_owner_prepare: null pointer");
     return launch_owner_prepare(a, local_rows, touched, n_touched, workspace, workspace_bytes,
                                 dw::as_stream(stream));
 }
@@ -3496,15 +3406,16 @@ int dw_sgns_owner_touch_claim(const int32_t *walks, int64_t n_walks, int32_t wal
                               int32_t context_radius, int64_t vocab_size, int32_t *claim,
                               int32_t step, uint32_t *touched, int64_t *n_touched,
                               uint32_t *fresh, int64_t *n_fresh, int32_t flags, void *stream) {
-    DW_REQUIRE(context_radius >= 1 && walk_length >= 2 * context_radius + 1 && n_walks >= 0 &&
-                   vocab_size >= 1 && step >= 1,
-               "dw_sgns_owner_touch_claim: bad sizes");
+    WalkShape sh;
+    int rc = walk_shape("dw_sgns_owner_touch_claim", walks, n_walks, walk_length, context_radius,
+                        0, vocab_size >= 1 && step >= 1, &sh);
+    if (rc != DW_OK) return rc;
     DW_REQUIRE(claim && touched && n_touched && (walks || n_walks == 0) && (!fresh || n_fresh),
                "dw_sgns_owner_touch_claim: null pointer");
     const hipStream_t st = dw::as_stream(stream);
     const dw_step_scalars *dyn = nullptr;
     int32_t delta = 0;
-    const int rc = dw::bound_step_rel(step, &dyn, &delta, "dw_sgns_owner_touch_claim");
+    rc = dw::bound_step_rel(step, &dyn, &delta, "dw_sgns_owner_touch_claim");
     if (rc != DW_OK) return rc;
     DW_REQUIRE((flags & ~1) == 0, "dw_sgns_owner_touch_claim: flags must be 0 or 1");
     // flags & 1: the caller zeroed the counters (owner_lazy_steps: one ring of counters per
@@ -3515,12 +3426,9 @@ int dw_sgns_owner_touch_claim(const int32_t *walks, int64_t n_walks, int32_t wal
         dw::set_error("dw_sgns_owner_touch_claim: counter reset failed");
         return DW_E_HIP;
     }
-    const int64_t n_centres = n_walks * (walk_length - 2 * context_radius);
-    if (n_centres == 0) return DW_OK;
-    int64_t blocks = (n_centres + 255) / 256;
-    if (blocks > grid_cap(8)) blocks = grid_cap(8);
-    hipLaunchKernelGGL(k_touch_claim, dim3((unsigned)blocks), dim3(256), 0, st, walks, n_centres,
-                       walk_length, context_radius, vocab_size, claim, step, dyn, delta, touched,
+    if (sh.n_centres == 0) return DW_OK;
+    hipLaunchKernelGGL(k_touch_claim, dim3(grid_for(sh.n_centres, 256, 0, grid_cap(8))), dim3(256),
+                       0, st, walks, sh.n_centres, walk_length, context_radius, vocab_size, claim, step, dyn, delta, touched,
                        reinterpret_cast<unsigned long long *>(n_touched), fresh,
                        reinterpret_cast<unsigned long long *>(n_fresh));
     DW_LAUNCH_CHECK("dw_sgns_owner_touch_claim");
@@ -3535,18 +3443,14 @@ int dw_sgns_owner_pass1(const int32_t *walks, int64_t n_walks, int32_t walk_leng
                         const int64_t *noise, uint64_t seed, uint64_t noise_offset,
                         float grad_scale, double *loss_acc, int32_t *status, void *workspace,
                         size_t workspace_bytes, void *stream) {
-    DW_REQUIRE(context_radius >= 1 && walk_length >= 2 * context_radius + 1 && n_walks >= 0 &&
-                   dim >= 1 && vocab_size >= 1 && neg_samples >= 0,
-               "dw_sgns_owner_pass1: bad sizes");
-    DW_REQUIRE((walks || n_walks == 0) && w_in && w_out_local && g_in && status,
-               "dw_sgns_owner_pass1: null pointer");
     SgnsArgs a = base_args(vocab_size, dim, neg_samples, w_in, w_out_local, g_in, nullptr, noise,
                            seed, noise_offset, grad_scale, loss_acc, status);
-    a.walks = walks;
-    a.L = walk_length;
-    a.R = context_radius;
-    a.batch = n_walks * (walk_length - 2 * context_radius);
-    a.C = 2 * context_radius;
+    WalkShape sh;
+    const int rc = walk_shape("dw_sgns_owner_pass1", walks, n_walks, walk_length, context_radius,
+                              neg_samples, dim >= 1 && vocab_size >= 1, &sh, &a);
+    if (rc != DW_OK) return rc;
+    DW_REQUIRE((walks || n_walks == 0) && w_in && w_out_local && g_in && status,
+               "dw_sgns_owner_pass1: null pointer");
     a.owner = owner;
     a.n_owners = n_owners;
     a.own_shift = -1;
@@ -3563,22 +3467,20 @@ int dw_sgns_owner_pass2(int64_t n_walks, int32_t walk_length, int32_t context_ra
                         float one_minus_beta2, float bias_correction2_sqrt, float neg_step_size,
                         float eps, float weight_decay, int32_t *status, void *workspace,
                         size_t workspace_bytes, int64_t *n_records, void *stream) {
-    DW_REQUIRE(context_radius >= 1 && walk_length >= 2 * context_radius + 1 && n_walks >= 0 &&
-                   dim >= 1 && local_rows >= 1 && neg_samples >= 0,
-               "dw_sgns_owner_pass2: bad sizes");
+    WalkShape sh;
+    const int rc = walk_shape("dw_sgns_owner_pass2", nullptr, n_walks, walk_length, context_radius,
+                              neg_samples, dim >= 1 && local_rows >= 1, &sh);
+    if (rc != DW_OK) return rc;
     DW_REQUIRE(w_in && g_out_local && status, "dw_sgns_owner_pass2: null pointer");
     const bool adam = m_out != nullptr;
     DW_REQUIRE(!adam || (v_out && row_flags && w_out_local && bias_correction2_sqrt > 0.f),
                "dw_sgns_owner_pass2: the fused Adam needs w_out_local, m, v, flags, scalars");
-    OutAdam oa{w_out_local, m_out, v_out, row_flags,
-               dw::AdamScalars{one_minus_beta1, beta2, one_minus_beta2, bias_correction2_sqrt,
-                               neg_step_size, eps, weight_decay,
-                               bias_correction2_sqrt > 0.f ? 1.0f / bias_correction2_sqrt : 0.f}};
-    oa.dyn = dw::bound_step_scalars();
-    const int64_t T = 2 * (int64_t)context_radius * (1 + neg_samples);
-    return launch_owner_pass2(n_walks * (walk_length - 2 * context_radius), T, local_rows, dim,
-                              w_in, g_out_local, adam ? &oa : nullptr, workspace,
-                              workspace_bytes, n_records, dw::as_stream(stream));
+    const OutAdam oa = fused_adam(w_out_local, m_out, v_out, row_flags, one_minus_beta1, beta2,
+                                  one_minus_beta2, bias_correction2_sqrt, neg_step_size, eps,
+                                  weight_decay);
+    return launch_owner_pass2(sh.n_centres, sh.T, local_rows, dim, w_in, g_out_local,
+                              adam ? &oa : nullptr, workspace, workspace_bytes, n_records,
+                              dw::as_stream(stream));
 }
 
 int dw_sgns_owner_pass2_lazy(int64_t n_walks, int32_t walk_length, int32_t context_radius,
@@ -3588,9 +3490,10 @@ int dw_sgns_owner_pass2_lazy(int64_t n_walks, int32_t walk_length, int32_t conte
                              int32_t step, int32_t flags, uint32_t *counts, int32_t *status,
                              void *workspace, size_t workspace_bytes, int64_t *n_records,
                              void *stream) {
-    DW_REQUIRE(context_radius >= 1 && walk_length >= 2 * context_radius + 1 && n_walks >= 0 &&
-                   dim >= 1 && local_rows >= 1 && neg_samples >= 0 && step >= 1,
-               "dw_sgns_owner_pass2_lazy: bad sizes");
+    WalkShape sh;
+    int rc = walk_shape("dw_sgns_owner_pass2_lazy", nullptr, n_walks, walk_length, context_radius,
+                        neg_samples, dim >= 1 && local_rows >= 1 && step >= 1, &sh);
+    if (rc != DW_OK) return rc;
     DW_REQUIRE(w_in && w_out_local && g_out_local && m_out && v_out && last_step && hist &&
                    status,
                "dw_sgns_owner_pass2_lazy: null pointer");
@@ -3601,12 +3504,11 @@ int dw_sgns_owner_pass2_lazy(int64_t n_walks, int32_t walk_length, int32_t conte
     oa.betas_const = (flags & 4) != 0;
     oa.counts = nullptr;   // (placed records: the catch-up's scan cleared the counts)
     (void)counts;
-    const int rc = dw::bound_step_rel(step, &oa.dyn, &oa.step_delta, "dw_sgns_owner_pass2_lazy");
+    rc = dw::bound_step_rel(step, &oa.dyn, &oa.step_delta, "dw_sgns_owner_pass2_lazy");
     if (rc != DW_OK) return rc;
-    const int64_t T = 2 * (int64_t)context_radius * (1 + neg_samples);
-    return launch_owner_pass2(n_walks * (walk_length - 2 * context_radius), T, local_rows, dim,
-                              w_in, g_out_local, &oa, workspace, workspace_bytes, n_records,
-                              dw::as_stream(stream), (flags & 1) != 0);
+    return launch_owner_pass2(sh.n_centres, sh.T, local_rows, dim, w_in, g_out_local, &oa,
+                              workspace, workspace_bytes, n_records, dw::as_stream(stream),
+                              (flags & 1) != 0);
 }
 
 int dw_sgns_owner_out_rows(const int32_t *walks, int64_t n_walks, int32_t walk_length,
@@ -3618,35 +3520,31 @@ int dw_sgns_owner_out_rows(const int32_t *walks, int64_t n_walks, int32_t walk_l
                            uint32_t *counts, uint8_t *pending, const float *hist,
                            int32_t step, double *loss_acc, int32_t *status,
                            void *workspace, size_t workspace_bytes, void *stream) {
-    DW_REQUIRE(context_radius >= 1 && walk_length >= 2 * context_radius + 1 && n_walks >= 0 &&
-                   dim >= 1 && vocab_size >= 1 && neg_samples >= 0 && n_owners >= 1 &&
-                   owner >= 0 && owner < n_owners && local_rows >= 1 && step >= 1,
-               "dw_sgns_owner_out_rows: bad sizes");
+    SgnsArgs a = base_args(vocab_size, dim, neg_samples, w_in, w_out_local, nullptr, g_out_local,
+                           noise, seed, noise_offset, grad_scale, loss_acc, status);
+    WalkShape sh;
+    int rc = walk_shape("dw_sgns_owner_out_rows", walks, n_walks, walk_length, context_radius,
+                        neg_samples,
+                        dim >= 1 && vocab_size >= 1 && n_owners >= 1 && owner >= 0 &&
+                            owner < n_owners && local_rows >= 1 && step >= 1,
+                        &sh, &a);
+    if (rc != DW_OK) return rc;
+    const int64_t T = sh.T, n_centres = sh.n_centres;
     DW_REQUIRE(dim % 64 == 0 && dim <= 512, "dw_sgns_owner_out_rows: needs dim a multiple of 64 "
                "(<= 512)");
-    DW_REQUIRE(2 * (int64_t)context_radius * (1 + neg_samples) <= G16_TMAX,
-               "dw_sgns_owner_out_rows: 2R(1+K) must be <= %d", G16_TMAX);
+    DW_REQUIRE(T <= G16_TMAX, "dw_sgns_owner_out_rows: 2R(1+K) must be <= %d", G16_TMAX);
     DW_REQUIRE(local_rows * n_owners >= vocab_size && vocab_size <= 0x7FFFFFFF,
                "dw_sgns_owner_out_rows: the owners' rows do not cover the vocabulary");
     if (n_walks == 0) return DW_OK;
     DW_REQUIRE(walks && w_in && w_out_local && g_out_local && m_out && v_out && last_step &&
                    counts && pending && hist && status,
                "dw_sgns_owner_out_rows: null pointer");
-    const int64_t T = 2 * (int64_t)context_radius * (1 + neg_samples);
-    const int64_t n_centres = n_walks * (walk_length - 2 * context_radius);
     hipStream_t st = dw::as_stream(stream);
-    SgnsArgs a = base_args(vocab_size, dim, neg_samples, w_in, w_out_local, nullptr, g_out_local,
-                           noise, seed, noise_offset, grad_scale, loss_acc, status);
-    a.walks = walks;
-    a.L = walk_length;
-    a.R = context_radius;
-    a.batch = n_centres;
-    a.C = 2 * context_radius;
     a.owner = owner;
     a.n_owners = n_owners;
     int32_t fl = 0;
     dw::Fixed fx;
-    int rc = exact_of(g_out_local, local_rows * dim, &fx, &fl, "dw_sgns_owner_out_rows");
+    rc = exact_of(g_out_local, local_rows * dim, &fx, &fl, "dw_sgns_owner_out_rows");
     if (rc != DW_OK) return rc;
     Workspace ws;
     OwnerLayout lay;
@@ -3672,30 +3570,19 @@ int dw_sgns_owner_out_rows(const int32_t *walks, int64_t n_walks, int32_t walk_l
     // 0.3%, profiles/r06_pipe_order_ab.txt)
     int32_t gch = static_cast<int32_t>((bound + 2 * resident - 1) / (2 * resident));
     gch = gch < 16 ? 16 : gch > 64 ? 64 : gch;
-    int64_t blocks = ((bound + gch - 1) / gch + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-    if (blocks > 65536) blocks = 65536;
-    if (blocks < 1) blocks = 1;
-    const dim3 g((unsigned)blocks), bl(WAVES_PER_BLOCK * WAVE);
+    const dim3 g(grid_for((bound + gch - 1) / gch, WAVES_PER_BLOCK, 1, 65536)),
+        bl(WAVES_PER_BLOCK * WAVE);
     float *cs = reinterpret_cast<float *>(ws.v0);
-#define DW_OUT_ROWS(F, X)                                                                       \
-    hipLaunchKernelGGL((k_out_rows<F, X>), g, bl, 0, st, a, ws.k1, ws.v1, ws.bounds, gch, oa,    \
-                       cs, fx, pl.off)
-    switch ((dim / 64) * 2 + (fx.acc ? 1 : 0)) {
-        case 2: DW_OUT_ROWS(1, false); break;
-        case 3: DW_OUT_ROWS(1, true); break;
-        case 4: DW_OUT_ROWS(2, false); break;
-        case 5: DW_OUT_ROWS(2, true); break;
-        case 8: DW_OUT_ROWS(4, false); break;
-        case 9: DW_OUT_ROWS(4, true); break;
-        case 16: DW_OUT_ROWS(8, false); break;
-        case 17: DW_OUT_ROWS(8, true); break;
-        default:
-            dw::set_error("dw_sgns_owner_out_rows: d must be one of 64, 128, 256, 512 (got %d)", dim);
-            return DW_E_UNSUPPORTED;
-    }
-#undef DW_OUT_ROWS
-    DW_LAUNCH_CHECK("dw_sgns_owner_out_rows/rows");
-    return DW_OK;   // (every row stepped whole by the range it starts in)
+    // (every row stepped whole by the range it starts in)
+    rc = for_width(dim, true, fx.acc != nullptr, [&](auto f4, auto, auto x) -> int {
+        hipLaunchKernelGGL((k_out_rows<decltype(f4)::value, decltype(x)::value>), g, bl, 0, st, a,
+                           ws.k1, ws.v1, ws.bounds, gch, oa, cs, fx, pl.off);
+        DW_LAUNCH_CHECK("dw_sgns_owner_out_rows/rows");
+        return DW_OK;
+    });
+    if (rc == DW_E_UNSUPPORTED)
+        dw::set_error("dw_sgns_owner_out_rows: d must be one of 64, 128, 256, 512 (got %d)", dim);
+    return rc;
 }
 
 int dw_sgns_pairs(const int64_t *inputs, const int64_t *targets, int64_t batch, int32_t n_ctx,
@@ -3745,9 +3632,7 @@ int dw_sgns_noise(int64_t batch, int32_t n_ctx, int32_t neg_samples, int64_t voc
     const int64_t n = batch * n_ctx * neg_samples;
     if (n == 0) return DW_OK;
     DW_REQUIRE(noise, "dw_sgns_noise: null pointer");
-    int64_t blocks = (n + 255) / 256;
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(k_noise_fill, dim3((unsigned)blocks), dim3(256), 0,
+    hipLaunchKernelGGL(k_noise_fill, dim3(grid_for(n, 256, 0, 65536)), dim3(256), 0,
                        dw::as_stream(stream), batch, n_ctx, neg_samples, vocab_size,
                        static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32),
                        noise_offset, noise);
@@ -3758,16 +3643,11 @@ int dw_sgns_noise(int64_t batch, int32_t n_ctx, int32_t neg_samples, int64_t voc
 int dw_embedding_renorm_workspace_bytes(int64_t n_ids, int64_t vocab_size, size_t *bytes) {
     DW_REQUIRE(bytes && n_ids >= 0 && vocab_size >= 1 && vocab_size < 0x7FFFFFFF,
                "dw_embedding_renorm_workspace_bytes: bad arguments");
-    size_t tmp = 0;
-    rocprim::double_buffer<uint32_t> kb(nullptr, nullptr);
-    hipError_t e = rocprim::radix_sort_keys<RenormSortConfig>(
-        nullptr, tmp, kb, static_cast<uint32_t>(n_ids > 0 ? n_ids : 1), 0,
-        end_bit_for(vocab_size + 1), nullptr);
-    if (e != hipSuccess) {
-        dw::set_error("dw_embedding_renorm: sort size query failed: %s", hipGetErrorString(e));
-        return DW_E_HIP;
-    }
-    *bytes = 2 * align256(static_cast<size_t>(n_ids) * 4) + align256(tmp);
+    RenormBufs p;
+    Arena a{nullptr};
+    const int rc = plan_renorm(a, n_ids, vocab_size, &p);
+    if (rc != DW_OK) return rc;
+    *bytes = a.off;
     return DW_OK;
 }
 
@@ -3779,31 +3659,25 @@ int dw_embedding_renorm(float *weight, int64_t vocab_size, int32_t dim, const in
     if (n_ids == 0) return DW_OK;
     DW_REQUIRE(weight && ids && workspace && status, "dw_embedding_renorm: null pointer");
     DW_REQUIRE(n_ids < 0x7FFFFFFF, "dw_embedding_renorm: too many ids");
-    size_t need = 0;
-    int rc = dw_embedding_renorm_workspace_bytes(n_ids, vocab_size, &need);
+    RenormBufs p;
+    Arena a{static_cast<char *>(workspace)};
+    const int rc = plan_renorm(a, n_ids, vocab_size, &p);
     if (rc != DW_OK) return rc;
-    DW_REQUIRE(workspace_bytes >= need, "dw_embedding_renorm: workspace too small (%zu < %zu)",
-               workspace_bytes, need);
+    DW_REQUIRE(workspace_bytes >= a.off, "dw_embedding_renorm: workspace too small (%zu < %zu)",
+               workspace_bytes, a.off);
     hipStream_t st = dw::as_stream(stream);
-    char *p = static_cast<char *>(workspace);
-    const size_t kbytes = align256(static_cast<size_t>(n_ids) * 4);
-    uint32_t *k0 = reinterpret_cast<uint32_t *>(p), *k1 = reinterpret_cast<uint32_t *>(p + kbytes);
     hipLaunchKernelGGL(k_renorm_keys, dim3((unsigned)((n_ids + 255) / 256)), dim3(256), 0, st,
-                       ids, n_ids, vocab_size, k0, status);
+                       ids, n_ids, vocab_size, p.k0, status);
     DW_LAUNCH_CHECK("dw_embedding_renorm/keys");
-    rocprim::double_buffer<uint32_t> kb(k0, k1);
-    size_t tmp = need - 2 * kbytes;
+    rocprim::double_buffer<uint32_t> kb(p.k0, p.k1);
     hipError_t e = rocprim::radix_sort_keys<RenormSortConfig>(
-        p + 2 * kbytes, tmp, kb, static_cast<uint32_t>(n_ids), 0, end_bit_for(vocab_size + 1),
-        st);
+        p.tmp, p.tmp_bytes, kb, static_cast<uint32_t>(n_ids), 0, end_bit_for(vocab_size + 1), st);
     if (e != hipSuccess) {
         dw::set_error("dw_embedding_renorm: sort failed: %s", hipGetErrorString(e));
         return DW_E_HIP;
     }
-    int64_t blocks = (n_ids + 3) / 4;
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(k_renorm_rows, dim3((unsigned)blocks), dim3(256), 0, st, kb.current(),
-                       n_ids, vocab_size, weight, dim, max_norm);
+    hipLaunchKernelGGL(k_renorm_rows, dim3(grid_for(n_ids, 4, 0, 65536)), dim3(256), 0, st,
+                       kb.current(), n_ids, vocab_size, weight, dim, max_norm);
     DW_LAUNCH_CHECK("dw_embedding_renorm/rows");
     return DW_OK;
 }
@@ -3816,10 +3690,8 @@ int dw_pooled_logits(const int64_t *inputs, int32_t n_in, const int64_t *outputs
     if (batch == 0 || n_out == 0) return DW_OK;
     DW_REQUIRE(inputs && outputs && w_in && w_out && logits && status,
                "dw_pooled_logits: null pointer");
-    int64_t blocks = (batch + 3) / 4;
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(k_logits, dim3((unsigned)blocks), dim3(256), 0, dw::as_stream(stream),
-                       inputs, n_in, outputs, batch, n_out, vocab_size, dim, w_in, w_out, proba,
+    hipLaunchKernelGGL(k_logits, dim3(grid_for(batch, 4, 0, 65536)), dim3(256), 0,
+                       dw::as_stream(stream), inputs, n_in, outputs, batch, n_out, vocab_size, dim, w_in, w_out, proba,
                        logits, status);
     DW_LAUNCH_CHECK("dw_pooled_logits");
     return DW_OK;
@@ -3834,10 +3706,8 @@ int dw_pooled_logits_backward(const int64_t *inputs, int32_t n_in, const int64_t
     if (batch == 0 || n_out == 0) return DW_OK;
     DW_REQUIRE(inputs && outputs && w_in && w_out && dlogits && g_in && g_out && status,
                "dw_pooled_logits_backward: null pointer");
-    int64_t blocks = (batch + 3) / 4;
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(k_logits_bwd, dim3((unsigned)blocks), dim3(256), 0, dw::as_stream(stream),
-                       inputs, n_in, outputs, batch, n_out, vocab_size, dim, w_in, w_out, dlogits,
+    hipLaunchKernelGGL(k_logits_bwd, dim3(grid_for(batch, 4, 0, 65536)), dim3(256), 0,
+                       dw::as_stream(stream), inputs, n_in, outputs, batch, n_out, vocab_size, dim, w_in, w_out, dlogits,
                        g_in, g_out, status);
     DW_LAUNCH_CHECK("dw_pooled_logits_backward");
     return DW_OK;

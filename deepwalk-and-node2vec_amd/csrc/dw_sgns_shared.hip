@@ -246,9 +246,7 @@ extern "C" int dw_sgns_walks_shared(const int32_t *walks, int64_t n_walks, int32
                                     const float *w_out, float *g_in, float *g_out,
                                     const int64_t *shared_ids, float grad_scale, double *loss_acc,
                                     int32_t *status, void *stream) {
-    DW_REQUIRE(context_radius >= 1, "dw_sgns_walks_shared: context_radius must be >= 1");
-    DW_REQUIRE(walk_length >= 2 * context_radius + 1,
-               "dw_sgns_walks_shared: walk_length %d < 2R+1 (Text is too short!)", walk_length);
+    if (int rc = dw::require_window("dw_sgns_walks_shared", walk_length, context_radius)) return rc;
     DW_REQUIRE(walk_length <= MAX_L, "dw_sgns_walks_shared: walk_length %d > %d is not supported",
                walk_length, MAX_L);
     DW_REQUIRE(dim == 64 || dim == 128 || dim == 256,

@@ -543,3 +543,74 @@ def test_fused_out_table_adam_equals_unfused(hip_device, d, nw):
         assert_no_row_drift(a.cpu().numpy(), b.cpu().numpy())
     np.testing.assert_allclose(fused.m.cpu().numpy(), plain.m.cpu().numpy(), rtol=1e-3,
                                atol=1e-6)
+
+
+def test_workspace_query_and_call_agree(hip_device):
+    """Every *_workspace_bytes query and the call it sizes run the same plan, so they cannot
+    disagree: at V = 50, d = 64, K = 2 a call given exactly the queried bytes succeeds, and the
+    same call given 256 bytes (one buffer's alignment) fewer is refused with DW_E_INVALID_ARG and
+    a 'workspace too small' message before anything is launched."""
+    import ctypes
+    lib = _native.load()
+    st = _native.stream(hip_device)
+    V, d, K, R, L, n = 50, 64, 2, 2, 8, 2
+    gen = torch.Generator().manual_seed(11)
+    w_in = torch.randn(V, d, generator=gen).to(hip_device)
+    w_out = torch.randn(V, d, generator=gen).to(hip_device)
+    g_in, g_out = torch.zeros_like(w_in), torch.zeros_like(w_out)
+    acc = torch.zeros(4, dtype=torch.float64, device=hip_device)
+    status = torch.zeros(1, dtype=torch.int32, device=hip_device)
+    walks = torch.randint(1, V, (n, L), generator=gen, dtype=torch.int32).to(hip_device)
+    tail = (V, d, _native.ptr(w_in), _native.ptr(w_out), _native.ptr(g_in), _native.ptr(g_out),
+            None, 7, 0, 1.0, _native.ptr(acc), _native.ptr(status))
+
+    def query(name, *args):
+        nbytes = ctypes.c_size_t(0)
+        _native.call(name, *args, ctypes.byref(nbytes))
+        assert nbytes.value > 256 and nbytes.value % 256 == 0, (name, nbytes.value)
+        return nbytes.value
+
+    def check(name, nbytes, head, rest=(), short_refused=True):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=hip_device)
+        fn = getattr(lib, name)
+        if short_refused:
+            rc = fn(*head, _native.ptr(ws), nbytes - 256, *rest, st)
+            err = lib.dw_last_error_string()
+            assert rc == _native.DW_E_INVALID_ARG and b'workspace too small' in err, (name, rc, err)
+        rc = fn(*head, _native.ptr(ws), nbytes, *rest, st)
+        assert rc == _native.DW_OK, (name, rc, lib.dw_last_error_string())
+        torch.cuda.synchronize()
+
+    # dw_sgns_pairs: batch 3, n_ctx 2
+    inputs = torch.randint(0, V, (3,), generator=gen).to(hip_device)
+    targets = torch.randint(0, V, (3, 2), generator=gen).to(hip_device)
+    check('dw_sgns_pairs', query('dw_sgns_workspace_bytes', 3, 2, K, V),
+          (_native.ptr(inputs), _native.ptr(targets), 3, 2, K) + tail)
+
+    # dw_sgns_walks: the query covers the aggregated layout, the larger one here (80 records
+    # against 96 round to the same key / value bytes; the coefficients and aggregate rows are on
+    # top); with aggregation off the call needs less than the query returns
+    wbytes = query('dw_sgns_walks_workspace_bytes', n, L, R, K, V, d)
+    assert wbytes > query('dw_sgns_workspace_bytes', n * (L - 2 * R), 2 * R, K, V)
+    head = (_native.ptr(walks), n, L, R, K) + tail
+    try:
+        _native.call('dw_sgns_set_walk_agg', 1)
+        check('dw_sgns_walks', wbytes, head)
+        _native.call('dw_sgns_set_walk_agg', 0)
+        check('dw_sgns_walks', wbytes, head, short_refused=False)
+    finally:
+        _native.call('dw_sgns_set_walk_agg', -1)
+
+    # dw_sgns_owner_prepare: one owner, local_rows = V
+    touched = torch.zeros(n * (L - 2 * R), dtype=torch.int32, device=hip_device)
+    n_touched = torch.zeros(1, dtype=torch.int64, device=hip_device)
+    check('dw_sgns_owner_prepare',
+          query('dw_sgns_owner_workspace_bytes', n * (L - 2 * R), 2 * R, K, V, V),
+          (_native.ptr(walks), n, L, R, K, V, V, _native.ptr(touched), _native.ptr(n_touched)))
+    assert 1 <= int(n_touched) <= n * (L - 2 * R)
+
+    # dw_embedding_renorm: 5 ids
+    ids = torch.randint(0, V, (5,), generator=gen).to(hip_device)
+    check('dw_embedding_renorm', query('dw_embedding_renorm_workspace_bytes', 5, V),
+          (_native.ptr(w_in), V, d, _native.ptr(ids), 5, 1.0), rest=(_native.ptr(status),))
+    _native.check_status(status, 'test_workspace_query_and_call_agree')
