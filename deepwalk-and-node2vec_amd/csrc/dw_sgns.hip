@@ -48,7 +48,9 @@ constexpr int WAVES_PER_BLOCK = 4;
 constexpr int CHUNK = 12;            // output rows in flight per wave
 constexpr int TMAX = 256;            // max output rows per centre in records mode
 constexpr int GCH = 512;             // records per pass-2 wave chunk (large batches; pass2_chunk)
-constexpr int GU = 8;                // records in flight per pass-2 iteration
+constexpr int GU = 8;                // row loads (256 B each) in flight per pass-2 wave
+constexpr int GATHER_WAVES = 3;      // pass-2 waves per SIMD while the chunks stay at GCH
+constexpr int VMCNT0 = 0x0F70;       // s_waitcnt vmcnt(0) alone (expcnt 7, lgkmcnt 15: no wait)
 constexpr uint32_t TAG_SGNS = 0x53470000u;  // 'SG'
 
 __device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
@@ -910,23 +912,48 @@ struct OutAdam {
     uint8_t *pend = nullptr;
 };
 
-// One row's lazy Adam step (one wave, VPL elements per lane): replay the missed steps, apply
-// `step` (oa.step, or the bound block's) with g (registers), record the step.
+// One row's lazy Adam state as a wave holds it (VPL elements per lane): p, m, v, the step the
+// row was last stepped at and whether its parameter half is pending. Loaded by lazy_row_load —
+// k_rec_gather issues it when the row begins, many records before lazy_row_apply needs it.
+template <int VPL>
+struct LazyRow {
+    float p[VPL], m[VPL], v[VPL];
+    int32_t from;
+    bool pd;
+};
+
 template <int VPL, bool MASKED>
-__device__ __forceinline__ void lazy_row_step(const OutAdam &oa, int32_t step, uint32_t row,
-                                              int32_t d, int lane, const float (&g)[VPL]) {
+__device__ __forceinline__ void lazy_row_load(const OutAdam &oa, uint32_t row, int32_t d, int lane,
+                                              LazyRow<VPL> &r) {
     // (row is wave-uniform; lanes past d carry zeros through a uniform replay loop)
-    const int32_t from = __builtin_amdgcn_readfirstlane(oa.last[row]);
-    const bool pd = oa.pend && __builtin_amdgcn_readfirstlane(oa.pend[row]) != 0;
+    r.from = __builtin_amdgcn_readfirstlane(oa.last[row]);
+    r.pd = oa.pend && __builtin_amdgcn_readfirstlane(oa.pend[row]) != 0;
     const int64_t o = static_cast<int64_t>(row) * d + lane;
-    float pp[VPL], mm[VPL], vv[VPL], gg[VPL];
 #pragma unroll
     for (int m = 0; m < VPL; ++m) {
         const bool live = !MASKED || lane + WAVE * m < d;
         const int64_t i = o + WAVE * m;
-        pp[m] = live ? oa.p[i] : 0.f;
-        mm[m] = live ? oa.m[i] : 0.f;
-        vv[m] = live ? oa.v[i] : 0.f;
+        r.p[m] = live ? oa.p[i] : 0.f;
+        r.m[m] = live ? oa.m[i] : 0.f;
+        r.v[m] = live ? oa.v[i] : 0.f;
+    }
+}
+
+// One row's lazy Adam step from its loaded state: replay the missed steps, apply `step`
+// (oa.step, or the bound block's) with g (registers), record the step.
+template <int VPL, bool MASKED>
+__device__ __forceinline__ void lazy_row_apply(const OutAdam &oa, int32_t step, uint32_t row,
+                                               int32_t d, int lane, const float (&g)[VPL],
+                                               const LazyRow<VPL> &r) {
+    const int32_t from = r.from;
+    const bool pd = r.pd;
+    const int64_t o = static_cast<int64_t>(row) * d + lane;
+    float pp[VPL], mm[VPL], vv[VPL], gg[VPL];
+#pragma unroll
+    for (int m = 0; m < VPL; ++m) {
+        pp[m] = r.p[m];
+        mm[m] = r.m[m];
+        vv[m] = r.v[m];
         gg[m] = g[m];
     }
     if (oa.p_current) {
@@ -982,17 +1009,41 @@ __device__ __forceinline__ void lazy_row_step(const OutAdam &oa, int32_t step, u
     }
 }
 
+template <int VPL, bool MASKED>
+__device__ __forceinline__ void lazy_row_step(const OutAdam &oa, int32_t step, uint32_t row,
+                                              int32_t d, int lane, const float (&g)[VPL]) {
+    LazyRow<VPL> r;
+    lazy_row_load<VPL, MASKED>(oa, row, d, lane, r);
+    lazy_row_apply<VPL, MASKED>(oa, step, row, d, lane, g, r);
+}
+
 // range (row pieces, dw_sgns_walks_phase2_piece): only records [range[0], range[1]) — the
 // records of whole rows, so a piece's rows never continue in another piece's chunks.
 // EXACT: each term coef * w_in enters the row's int64 sum as a fixed-point integer (fo); a row
 // inside the chunk converts its exact sum back to float for the update, a straddling row adds
 // its integer part into fo.acc (k_fixed_boundary converts it once every chunk has).
-template <int VPL, bool MASKED, bool ADAM, bool EXACT = false>
+// The body. A chunk's records are staged 64 at a time, one per lane (a coalesced load of the keys
+// and one of the values per 64 records; the next 64 are loaded while these are consumed), and a
+// record's key, coefficient and centre come back wave-uniform through v_readlane: the row loads
+// keep a scalar base, and nothing scalar is loaded per record. A ballot of key[l] != key[l - 1]
+// marks where rows begin, so a group of GV records without a row start — most of them — is
+// GV x VPL loads issued back to back and then GV x VPL FMAs with no test between them; a group
+// with row starts is summed segment by segment in a rolled loop, the flush at its one site. When a
+// row begins its Adam state (p, m, v; the lazy form's last and pend) is loaded into registers:
+// issued before the gathers of the row's records, it has arrived at the flush, whose wait then
+// drains nothing younger. Lanes past the chunk's end repeat its last record; they are loaded (the
+// same row again) and never summed. A row's terms enter its sum in record order, one fmaf each.
+template <int VPL, bool MASKED, bool ADAM, bool LAZY, bool EXACT = false>
 __global__ void __launch_bounds__(WAVES_PER_BLOCK *WAVE)
     k_rec_gather(const uint32_t *__restrict__ keys, const uint64_t *__restrict__ vals,
                  int64_t n_rec, const float *__restrict__ w_in, float *__restrict__ g_out,
                  int32_t d, OutAdam oa, const int64_t *__restrict__ range, int32_t gch,
                  dw::Fixed fo, int32_t *status, const float *__restrict__ agg) {
+    static_assert(ADAM || !LAZY, "the lazy form is a fused-Adam form");
+    // records per group: GU row loads of 256 B in flight per wave whatever d (d = 512: two
+    // records). Deeper groups measured slower beside the in-table Adam (launch_pass2).
+    constexpr int GV = GU / VPL > 2 ? GU / VPL : 2;
+    static_assert(WAVE % GV == 0, "a staged block is whole groups");
     bool fx_range = false;
     uint32_t fx_tmax = 0u;   // EXACT: the largest |term|'s bits (the range test, at the end)
     const int lane = threadIdx.x & (WAVE - 1);
@@ -1012,20 +1063,53 @@ __global__ void __launch_bounds__(WAVES_PER_BLOCK *WAVE)
         const int64_t e1 = (e0 + gch < hi) ? e0 + gch : hi;
         const uint32_t before = e0 > lo ? keys[e0 - 1] : 0xFFFFFFFFu;
         const uint32_t after = e1 < hi ? keys[e1] : 0xFFFFFFFFu;
-        // lanes past the chunk's end repeat its LAST key: a partial final group must not switch
-        // `cur` back to an earlier row (that flushed the row a second time, with g = 0 — an extra
-        // Adam step in the fused form)
-        const uint32_t last = keys[e1 - 1];
-        uint32_t cur = keys[e0];
+        // lane l's record of the 64 from `base`: key, the key before it, centre field, coefficient
+        // (lanes past the chunk's end: its last record)
+        auto stage = [&](int64_t base, uint32_t &k, uint32_t &pk, uint32_t &ci, uint32_t &cf) {
+            const int64_t i = base + lane < e1 ? base + lane : e1 - 1;
+            const uint64_t v = vals[i];
+            k = keys[i];
+            pk = keys[i > e0 ? i - 1 : e0];
+            ci = static_cast<uint32_t>(v);
+            cf = static_cast<uint32_t>(v >> 32);
+        };
+        // (the explicit waits: the compiler places one wait count per loop header for every way
+        // into it, so a load still in flight on one way in — the first block's records here, a
+        // group's rows below — made every trip round the loop wait for the Adam-state loads the
+        // flush had just issued. Draining before the loop leaves its header nothing to wait for.)
+        uint32_t sk, spk, sci, scf;
+        stage(e0, sk, spk, sci, scf);
+        __builtin_amdgcn_s_waitcnt(VMCNT0);
+        uint32_t cur = __builtin_amdgcn_readfirstlane(sk);
         float g[VPL];
         int64_t gx[VPL];
-#pragma unroll
-        for (int m = 0; m < VPL; ++m) {
-            g[m] = 0.f;
-            gx[m] = 0;
-        }
-
         int64_t nt = 0;   // EXACT: the terms added to gx since the row began
+        // the row's Adam state, loaded when the row begins. (Unconditionally: a straddling row's
+        // is loaded and never used — nothing writes it during this kernel — so that the loads land
+        // in the registers the loop carries; behind a branch they were copied there, and the
+        // copies waited for them on the spot.)
+        float pp[VPL], mm[VPL], vv[VPL];
+        LazyRow<VPL> lr;
+        auto begin = [&](uint32_t row) {
+            nt = 0;
+#pragma unroll
+            for (int m = 0; m < VPL; ++m) {
+                g[m] = 0.f;
+                gx[m] = 0;
+            }
+            if constexpr (!ADAM) return;
+            if constexpr (LAZY) {
+                lazy_row_load<VPL, MASKED>(oa, row, d, lane, lr);
+            } else {
+                const int64_t o = static_cast<int64_t>(row) * d + lane;
+#pragma unroll
+                for (int m = 0; m < VPL; ++m) {
+                    pp[m] = live[m] ? oa.p[o + WAVE * m] : 0.f;
+                    mm[m] = live[m] ? oa.m[o + WAVE * m] : 0.f;
+                    vv[m] = live[m] ? oa.v[o + WAVE * m] : 0.f;
+                }
+            }
+        };
         auto flush = [&](uint32_t row) {
             float *dst = g_out + static_cast<int64_t>(row) * d + lane;
             if constexpr (EXACT) {
@@ -1042,19 +1126,22 @@ __global__ void __launch_bounds__(WAVES_PER_BLOCK *WAVE)
                 for (int m = 0; m < VPL; ++m) g[m] = dw::from_fixed(gx[m], fo.fi);
             }
             if (row != before && row != after) {
-                if (ADAM && oa.last) {
-                    lazy_row_step<VPL, MASKED>(oa, lstep, row, d, lane, g);
-                } else if (ADAM) {
+                if constexpr (LAZY) {
+                    lazy_row_apply<VPL, MASKED>(oa, lstep, row, d, lane, g, lr);
+                } else if constexpr (ADAM) {
+                    // every element's arithmetic, then the stores
                     const int64_t o = static_cast<int64_t>(row) * d + lane;
 #pragma unroll
                     for (int m = 0; m < VPL; ++m) {
+                        float gg = g[m];
+                        dw::adam_elem(pp[m], gg, mm[m], vv[m], sc);
+                    }
+#pragma unroll
+                    for (int m = 0; m < VPL; ++m) {
                         if (!live[m]) continue;
-                        const int64_t i = o + WAVE * m;
-                        float pp = oa.p[i], gg = g[m], mm = oa.m[i], vv = oa.v[i];
-                        dw::adam_elem(pp, gg, mm, vv, sc);
-                        oa.p[i] = pp;
-                        oa.m[i] = mm;
-                        oa.v[i] = vv;
+                        oa.p[o + WAVE * m] = pp[m];
+                        oa.m[o + WAVE * m] = mm[m];
+                        oa.v[o + WAVE * m] = vv[m];
                     }
                     if (lane == 0) oa.flags[row] = 1;
                 } else {
@@ -1068,49 +1155,74 @@ __global__ void __launch_bounds__(WAVES_PER_BLOCK *WAVE)
                     if (live[m]) atomicAdd(dst + WAVE * m, g[m]);
             }
         };
+        begin(cur);
 
-        for (int64_t e = e0; e < e1; e += GU) {
-            uint32_t k[GU];
-            float coef[GU];
-            float x[GU][VPL];
+        for (int64_t base = e0; base < e1; base += WAVE) {
+            const int nb = e1 - base < WAVE ? static_cast<int>(e1 - base) : WAVE;
+            // bit l: record l begins a row (the chunk's first record continues `cur`)
+            const uint64_t starts = __ballot(lane < nb && base + lane > e0 && sk != spk);
+            uint32_t nk = 0u, npk = 0u, nci = 0u, ncf = 0u;
+            if (base + WAVE < e1) stage(base + WAVE, nk, npk, nci, ncf);
+#pragma unroll 1
+            for (int j = 0; j < nb; j += GV) {
+                float coef[GV];
+                float x[GV][VPL];
 #pragma unroll
-            for (int u = 0; u < GU; ++u) {
-                const bool in = e + u < e1;
-                const uint64_t v = in ? vals[e + u] : 0ull;
-                k[u] = in ? keys[e + u] : last;
-                coef[u] = in ? __uint_as_float(static_cast<uint32_t>(v >> 32)) : 0.f;
-                // an aggregate record (k_walk_agg; never on the owner / lazy paths, agg == NULL)
-                // reads its precomputed row of agg instead of a centre row of w_in
-                const uint32_t ci = static_cast<uint32_t>(v);
-                const float *src = ((ci & AGG_BIT) ? agg : w_in) +
-                                   static_cast<int64_t>(ci & ~AGG_BIT) * d + lane;
+                for (int u = 0; u < GV; ++u) {
+                    // an aggregate record (k_walk_agg; never on the owner / lazy paths, agg == NULL)
+                    // reads its precomputed row of agg instead of a centre row of w_in
+                    const uint32_t ci = __builtin_amdgcn_readlane(sci, j + u);
+                    const float *src = ((ci & AGG_BIT) ? agg : w_in) +
+                                       static_cast<int64_t>(ci & ~AGG_BIT) * d + lane;
 #pragma unroll
-                for (int m = 0; m < VPL; ++m) x[u][m] = (in && live[m]) ? src[WAVE * m] : 0.f;
-            }
+                    for (int m = 0; m < VPL; ++m) x[u][m] = live[m] ? src[WAVE * m] : 0.f;
+                }
 #pragma unroll
-            for (int u = 0; u < GU; ++u) {
-                if (k[u] != cur) {
-                    flush(cur);
-                    cur = k[u];
-                    nt = 0;
+                for (int u = 0; u < GV; ++u)
+                    coef[u] = __uint_as_float(__builtin_amdgcn_readlane(scf, j + u));
+                auto add = [&](int u) {
+                    ++nt;
 #pragma unroll
                     for (int m = 0; m < VPL; ++m) {
-                        g[m] = 0.f;
-                        gx[m] = 0;
+                        if constexpr (EXACT) {
+                            const float t = coef[u] * x[u][m];
+                            gx[m] += dw::fixed_bits(t, fo.fs);
+                            fx_tmax = dw::fixed_track(fx_tmax, t);
+                        } else {
+                            g[m] = fmaf(coef[u], x[u][m], g[m]);
+                        }
                     }
-                }
-                ++nt;
+                };
+                const int n = nb - j < GV ? nb - j : GV;   // (the rest repeat the last record)
+                uint32_t bits = static_cast<uint32_t>(starts >> j) & ((1u << GV) - 1u);
+                if (bits == 0u && n == GV) {
 #pragma unroll
-                for (int m = 0; m < VPL; ++m) {
-                    if constexpr (EXACT) {
-                        const float t = coef[u] * x[u][m];
-                        gx[m] += dw::fixed_bits(t, fo.fs);
-                        fx_tmax = dw::fixed_track(fx_tmax, t);
-                    } else {
-                        g[m] += coef[u] * x[u][m];
+                    for (int u = 0; u < GV; ++u) add(u);
+                    continue;
+                }
+                // row starts inside the group: records [s, t) are `cur`'s, record t begins a row
+                __builtin_amdgcn_s_waitcnt(VMCNT0);
+                int s = 0;
+#pragma unroll 1
+                for (;;) {
+                    if (bits & (1u << s)) {
+                        flush(cur);
+                        cur = __builtin_amdgcn_readlane(sk, j + s);
+                        begin(cur);
+                        bits &= bits - 1u;
                     }
+                    const int t = bits ? __builtin_ctz(bits) : n;
+#pragma unroll
+                    for (int u = 0; u < GV; ++u)
+                        if (u >= s && u < t) add(u);
+                    if (t >= n) break;
+                    s = t;
                 }
             }
+            sk = nk;
+            spk = npk;
+            sci = nci;
+            scf = ncf;
         }
         flush(cur);
     }
@@ -1312,6 +1424,25 @@ int64_t grid_cap(int per_cu) {
         n_cu[dev] = v;
     }
     return (int64_t)n_cu[dev] * per_cu;
+}
+
+// Dynamic LDS bytes that keep a kernel of 4-wave blocks which uses no LDS at `waves` waves per
+// SIMD (blocks per CU): the CU's LDS shared out, rounded down to 4 KB, so that one block more does
+// not fit. 0 (no cap) where the device does not tell, or a block may not ask for that much.
+size_t lds_for_waves(int waves) {
+    static int per_cu[64] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+    if (per_cu[dev] == 0) {
+        int v = 0;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) !=
+                hipSuccess || v <= 0)
+            v = -1;
+        per_cu[dev] = v;
+    }
+    if (per_cu[dev] < 0) return 0;
+    const size_t b = static_cast<size_t>(per_cu[dev]) / waves / 4096 * 4096;
+    return b > 0 && b <= 65536 ? b : 0;
 }
 
 // Blocks of a launch over n items, `per` to a block: ceil(n / per) within [lo, cap] (lo = 0: no
@@ -1846,15 +1977,26 @@ int launch_pass2(const uint32_t *keys, const uint64_t *vals, int64_t n_rec, cons
     if (blocks < 1) blocks = 1;
     if (blocks > 65536) blocks = 65536;
     const dim3 g((unsigned)blocks), bl(WAVES_PER_BLOCK * WAVE);
+    // A batch whose chunks stay at GCH fills the chip, and the gather then runs at what HBM gives
+    // random 512-B rows: more loads in flight only lengthen the queues (its own, and those the
+    // side-stream in-table Adam waits in). Measured at C3: 3 waves per SIMD of 8 row
+    // loads each is the fastest form, so an unused LDS allocation holds the kernel there. Smaller
+    // batches are latency-bound and keep every wave the registers allow.
+    const size_t lds = gch == GCH ? lds_for_waves(GATHER_WAVES) : 0;
     const int rc = for_width(d, false, fo.acc != nullptr, [&](auto w, auto masked, auto x) -> int {
         constexpr int VPL = decltype(w)::value;
         constexpr bool MASKED = decltype(masked)::value, EXACT = decltype(x)::value;
-        if (oa)
-            hipLaunchKernelGGL((k_rec_gather<VPL, MASKED, true, EXACT>), g, bl, 0, st, keys, vals,
-                               n_rec, w_in, g_out, d, *oa, range, gch, fo, status, agg);
+        if (oa && oa->last)   // the lazy form carries the replay and no dense update
+            hipLaunchKernelGGL((k_rec_gather<VPL, MASKED, true, true, EXACT>), g, bl, lds, st, keys,
+                               vals, n_rec, w_in, g_out, d, *oa, range, gch, fo, status, agg);
+        else if (oa)
+            hipLaunchKernelGGL((k_rec_gather<VPL, MASKED, true, false, EXACT>), g, bl, lds, st,
+                               keys, vals, n_rec, w_in, g_out, d, *oa, range, gch, fo, status,
+                               agg);
         else
-            hipLaunchKernelGGL((k_rec_gather<VPL, MASKED, false, EXACT>), g, bl, 0, st, keys, vals,
-                               n_rec, w_in, g_out, d, OutAdam{}, range, gch, fo, status, agg);
+            hipLaunchKernelGGL((k_rec_gather<VPL, MASKED, false, false, EXACT>), g, bl, lds, st,
+                               keys, vals, n_rec, w_in, g_out, d, OutAdam{}, range, gch, fo,
+                               status, agg);
         DW_LAUNCH_CHECK("dw_sgns/gather");
         return DW_OK;
     });
