@@ -6,6 +6,11 @@
 // loss, the gradient and the predictions of one evaluation are one gather pass: the fp32 rows are
 // staged once per tile in LDS, widened exactly on use, and both products — the logits
 // Z = X W^T and the gradient G += R^T X — run on v_mfma_f64_16x16x4_f64.
+//
+// The same pass serves the multi-label task (one-vs-rest logistic regression, a departure: the
+// reference has no multi-label task): only the per-sample stage between the two products
+// differs, K sigmoids, a decision rule and per-class counts instead of one softmax. That stage,
+// with the label and prediction types it implies, is the kernel's policy M.
 #include "dw_common.h"
 
 namespace {
@@ -43,13 +48,235 @@ __host__ __device__ inline int64_t nc_blocks(int64_t n, int32_t dim) {
     return b < 1 ? 1 : b;
 }
 
+// ---- the per-sample stage ----------------------------------------------------------------------
+// A policy M names the label a sample carries (label_t in global memory, slot_t per staged
+// sample in LDS), what a dropped sample's prediction is, the scalar sums (NSC) and the length of
+// the tail that follows the gradient rows, and stage(): from the partial logits in s_z
+// ([P][TS][RS]) to the residuals R in part 0 (0 in the padded classes and for dropped samples),
+// the lane's share sb of the intercept column, the scalar sums sc and the predictions.
+
+struct NcSoftmax {
+    typedef int32_t label_t;
+    typedef int32_t pred_t;
+    typedef int32_t slot_t;   // the label; -1: contributes nothing, -2: no such sample
+    static constexpr bool COUNTS = false;
+    static constexpr int NSC = 2;   // loss, hits
+    static constexpr pred_t DROPPED = -1;
+    template <int TS>
+    struct Shared {
+        slot_t y[TS];
+    };
+    __host__ __device__ static constexpr int32_t tail(int32_t) { return NSC; }
+    __device__ static slot_t none() { return -2; }
+    __device__ static bool valid(int64_t id, label_t y, int64_t V, int32_t K) {
+        return id >= 0 && id < V && y >= 0 && y < K;
+    }
+    __device__ static slot_t slot(int64_t id, label_t y, int64_t V, int32_t K) {
+        return valid(id, y, V, K) ? y : -1;
+    }
+    __device__ static bool dropped(slot_t my) { return my == -1; }
+    __device__ static slot_t staged(slot_t my) { return my < 0 ? -1 : my; }
+
+    // softmax: L lanes per sample, lane j takes classes j, j + L, ...; a class's slot in part 0
+    // of s_z is read and written by its lane alone
+    template <class S, int NQ>
+    __device__ __forceinline__ static void stage(double *s_z, Shared<S::TS> &sh,
+                                                 const double *__restrict__ coef, int64_t ld,
+                                                 int32_t d, int32_t K, int tid, double (&sb)[NQ],
+                                                 double (&sc)[NSC], pred_t *__restrict__ pred,
+                                                 int64_t i0) {
+        constexpr int TS = S::TS, P = S::P, RS = S::RS, L = NC_THREADS / TS;
+        const int s = tid / L, j = tid % L;
+        const int32_t y = sh.y[s];
+        double *zrow = &s_z[s * RS];
+        double m = -INFINITY, zy = 0.0;
+        int32_t arg = 0x7fffffff;
+        for (int c = j; c < K; c += L) {
+            double zc = zrow[c];
+#pragma unroll
+            for (int p = 1; p < P; ++p) zc += s_z[(p * TS + s) * RS + c];
+            zc += coef[c * ld + d];
+            zrow[c] = zc;
+            if (zc > m) {   // ascending c: the lowest class of a tie stays
+                m = zc;
+                arg = c;
+            }
+            if (c == y) zy = zc;
+        }
+#pragma unroll
+        for (int off = 1; off < L; off <<= 1) {
+            const double om = __shfl_xor(m, off, 64);
+            const int32_t oa = __shfl_xor(arg, off, 64);
+            if (om > m || (om == m && oa < arg)) {
+                m = om;
+                arg = oa;
+            }
+            zy += __shfl_xor(zy, off, 64);   // one lane's is non-zero
+        }
+        double se = 0.0;
+        for (int c = j; c < K; c += L) {
+            const double e = exp(zrow[c] - m);
+            zrow[c] = e;
+            se += e;
+        }
+#pragma unroll
+        for (int off = 1; off < L; off <<= 1) se += __shfl_xor(se, off, 64);
+        const double inv = 1.0 / se;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const int c = j + q * L;
+            double r = 0.0;
+            if (y >= 0 && c < K) r = zrow[c] * inv - (c == y ? 1.0 : 0.0);
+            zrow[c] = r;
+            sb[q] += r;   // the intercept column: a plain sum, in trip order
+        }
+        if (j == 0 && y >= 0) {
+            sc[0] += m + log(se) - zy;
+            sc[1] += arg == y ? 1.0 : 0.0;
+            if (pred) pred[i0 + s] = arg;
+        }
+    }
+};
+
+// One-vs-rest: bit c of a sample's uint64 mask says it has label c; mask 0 is a sample of no
+// label. RULE 0 predicts class c when z_c > 0, RULE 1 the popcount(mask) classes of the highest
+// logits (ties to the lowest class). The tail is the loss, then tp[K], predicted[K], true[K].
+struct NcMask {
+    uint64_t mask;
+    int32_t state;   // 1: a sample, -1: contributes nothing, -2: no such sample
+};
+
+template <int RULE>
+struct NcOvr {
+    typedef uint64_t label_t;
+    typedef uint64_t pred_t;
+    typedef NcMask slot_t;
+    static constexpr bool COUNTS = true;
+    static constexpr int NSC = 1;   // loss
+    static constexpr pred_t DROPPED = 0;
+    template <int TS>
+    struct Shared {
+        slot_t y[TS];
+        // per class over the block's samples; 16 n bytes of ids and masks keep a block's share
+        // of n far below 2^32
+        uint32_t cnt[3][64];
+    };
+    __host__ __device__ static constexpr int32_t tail(int32_t K) { return NSC + 3 * K; }
+    __device__ static slot_t none() { return NcMask{0, -2}; }
+    __device__ static bool valid(int64_t id, label_t y, int64_t V, int32_t K) {
+        return id >= 0 && id < V && (K >= 64 || (y >> K) == 0);   // no shift by 64
+    }
+    __device__ static slot_t slot(int64_t id, label_t y, int64_t V, int32_t K) {
+        return NcMask{y, valid(id, y, V, K) ? 1 : -1};
+    }
+    __device__ static bool dropped(const slot_t &my) { return my.state == -1; }
+    __device__ static slot_t staged(const slot_t &my) { return my; }
+
+    // L lanes per sample, lane j takes classes j, j + L, ... First every lane completes its
+    // classes' logits in part 0 of s_z. The rank of a class reads all K of them, the other
+    // lanes' too: a barrier before it, and one after it, before the residuals overwrite them.
+    template <class S, int NQ>
+    __device__ __forceinline__ static void stage(double *s_z, Shared<S::TS> &sh,
+                                                 const double *__restrict__ coef, int64_t ld,
+                                                 int32_t d, int32_t K, int tid, double (&sb)[NQ],
+                                                 double (&sc)[NSC], pred_t *__restrict__ pred,
+                                                 int64_t i0) {
+        constexpr int TS = S::TS, P = S::P, RS = S::RS, L = NC_THREADS / TS;
+        const int s = tid / L, j = tid % L, lane = tid & 63;
+        const bool ok = sh.y[s].state == 1;
+        const uint64_t mask = sh.y[s].mask;
+        double *zrow = &s_z[s * RS];
+        for (int c = j; c < K; c += L) {
+            double zc = zrow[c];
+#pragma unroll
+            for (int p = 1; p < P; ++p) zc += s_z[(p * TS + s) * RS + c];
+            zrow[c] = zc + coef[c * ld + d];
+        }
+        uint32_t top = 0;   // bit q: class j + q L is among the sample's top k
+        if constexpr (RULE == 1) {
+            __syncthreads();
+            const int k = __popcll(mask);
+            // own classes ranked per sweep of the row: 4, or 2 where NQ is no multiple of 4 or
+            // the accumulators leave no registers (Kp = 64 with dim > 256)
+            constexpr int QB = NQ % 4 == 0 && S::KP * S::DP < 64 * 512 ? 4 : 2;
+#pragma unroll
+            for (int q0 = 0; q0 < NQ; q0 += QB) {
+                if (q0 * L >= K) break;   // uniform over the block
+                double zq[QB];
+                int32_t rank[QB];
+#pragma unroll
+                for (int u = 0; u < QB; ++u) {
+                    const int c = j + (q0 + u) * L;
+                    zq[u] = c < K ? zrow[c] : 0.0;
+                    rank[u] = 0;
+                }
+                for (int o = 0; o < K; ++o) {   // the padded classes enter no rank
+                    const double zo = zrow[o];
+#pragma unroll
+                    for (int u = 0; u < QB; ++u)
+                        rank[u] += zo > zq[u] || (zo == zq[u] && o < j + (q0 + u) * L);
+                }
+#pragma unroll
+                for (int u = 0; u < QB; ++u)
+                    if (j + (q0 + u) * L < K && rank[u] < k) top |= 1u << (q0 + u);
+            }
+            __syncthreads();
+        }
+        // the wave's lanes of this lane's classes; the first of them adds their count
+        const uint64_t peers = (L == 4 ? 0x1111111111111111ull : 0x0101010101010101ull) << j;
+        auto tally = [&](int which, int c, bool bit) {
+            const uint64_t votes = __ballot(bit) & peers;
+            if (lane < L && c < K) atomicAdd(&sh.cnt[which][c], (uint32_t)__popcll(votes));
+        };
+        double loss = 0.0;
+        uint64_t pm = 0;
+        // one class at a time, so that one exp and one log1p are live beside the accumulators;
+        // uniform over the wave (the votes)
+#pragma unroll 1
+        for (int q = 0; q * L < K; ++q) {
+            const int c = j + q * L;   // < 64
+            const bool on = ok && c < K;
+            const double z = on ? zrow[c] : 0.0;
+            const bool t = on && ((mask >> c) & 1);
+            const bool p = on && (RULE == 1 ? (top >> q) & 1 : z > 0.0);
+            // sigmoid(|z|) and sigmoid(-|z|) from one exp(-|z|): finite for every z
+            const double e = exp(-fabs(z));
+            const double hi = 1.0 / (1.0 + e), lo = e * hi;
+            if (on) {
+                zrow[c] = t ? -(z >= 0.0 ? lo : hi) : (z >= 0.0 ? hi : lo);   // sigmoid(z) - y
+                loss += (fmax(z, 0.0) - (t ? z : 0.0)) + log1p(e);
+            }
+            if (p) pm |= 1ull << c;
+            tally(0, c, p && t);
+            tally(1, c, p);
+            tally(2, c, t);
+        }
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const int c = j + q * L;
+            const double r = ok && c < K ? zrow[c] : 0.0;
+            zrow[c] = r;
+            sb[q] += r;   // the intercept column: a plain sum, in trip order
+        }
+#pragma unroll
+        for (int off = 1; off < L; off <<= 1) {
+            loss += __shfl_xor(loss, off, 64);
+            pm |= __shfl_xor(pm, off, 64);
+        }
+        if (j == 0 && ok) {
+            sc[0] += loss;
+            if (pred) pred[i0 + s] = pm;
+        }
+    }
+};
+
 // Lane maps of v_mfma_f64_16x16x4_f64, lane l: A[row l & 15][k = l >> 4],
 // B[k = l >> 4][col l & 15], D[row (l >> 4) + 4 reg][col l & 15], reg < 4.
 //
 // A trip: (1) the TS rows (zeros where the sample does not exist, its id or label is out of range
 // or the column is past dim) go from registers, where the previous trip prefetched them, to LDS;
 // (2) logits: sample tile `sub`, k range `part` per wave, A = X (sample x k), B = W^T (k x class),
-// partial logits to LDS; (3) softmax: 256 / TS lanes per sample share its classes, every exp
+// partial logits to LDS; (3) M::stage: 256 / TS lanes per sample share its classes, every exp
 // evaluated once, residuals R (0 in the padded classes and for dropped samples) overwrite the
 // logits; (4) gradient: wave w owns columns [16 CT w, 16 CT (w + 1)), A = R^T (class x sample),
 // B = X (sample x column), the TS samples are TS / 4 k steps.
@@ -57,20 +284,21 @@ __host__ __device__ inline int64_t nc_blocks(int64_t n, int32_t dim) {
 // Reproducible bit for bit: block b walks trips b, b + grid, ... in order, the accumulators are
 // private to a (wave, lane, register), the scalar sums are added in a fixed lane and wave order,
 // the block writes one partial row and dw::k_logreg_finish adds the rows in block order.
-template <int KT, int CT>
+template <int KT, int CT, class M>
 __global__ void __launch_bounds__(NC_THREADS)
-    k_node_softmax(const float *__restrict__ table, int64_t V, int32_t d,
-                   const int64_t *__restrict__ ids, const int32_t *__restrict__ labels, int64_t n,
-                   int32_t K, const double *__restrict__ coef, double *__restrict__ partial,
-                   int32_t *__restrict__ pred, int32_t *status, int32_t vec4) {
+    k_node_logreg(const float *__restrict__ table, int64_t V, int32_t d,
+                  const int64_t *__restrict__ ids, const typename M::label_t *__restrict__ labels,
+                  int64_t n, int32_t K, const double *__restrict__ coef,
+                  double *__restrict__ partial, typename M::pred_t *__restrict__ pred,
+                  int32_t *status, int32_t vec4) {
     typedef NcShape<KT, CT> S;
     constexpr int TS = S::TS, NS = S::NS, P = S::P, CH = S::CH, XS = S::XS, RS = S::RS;
     constexpr int NPF = S::NPF;
-    constexpr int L = NC_THREADS / TS;   // lanes per sample in the softmax
+    constexpr int L = NC_THREADS / TS;   // lanes per sample in the stage
     __shared__ __attribute__((aligned(16))) float s_x[TS * XS];
     __shared__ double s_z[64 * RS];   // [P][TS][RS] partial logits, then [TS][RS] residuals
-    __shared__ int32_t s_y[TS];       // the sample's label, -1: contributes nothing
-    __shared__ double s_sc[4][2];
+    __shared__ typename M::template Shared<TS> sh;   // the samples' labels (and counts)
+    __shared__ double s_sc[4][M::NSC];
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -84,7 +312,11 @@ __global__ void __launch_bounds__(NC_THREADS)
     for (int kt = 0; kt < KT; ++kt)
 #pragma unroll
         for (int c = 0; c < CT; ++c) acc[kt][c] = d4{0.0, 0.0, 0.0, 0.0};
-    double sum_loss = 0.0, sum_hit = 0.0;
+    double sc[M::NSC];   // the scalar sums
+#pragma unroll
+    for (int t = 0; t < M::NSC; ++t) sc[t] = 0.0;
+    if constexpr (M::COUNTS)   // the first trip's barriers come before the first count
+        if (tid < 3 * 64) (&sh.cnt[0][0])[tid] = 0;
 
     // A thread's chunks of a trip: chunk e = tid + 256 j is columns 4 (e % CH) ... + 3 of
     // sample e / CH.
@@ -100,8 +332,7 @@ __global__ void __launch_bounds__(NC_THREADS)
             const int64_t i = trip * TS + e / CH;
             const int64_t ic = i < n ? i : n - 1;
             const int64_t id = ids[ic];
-            const int32_t y = labels[ic];
-            const bool ok = i < n && 4 * (e % CH) < d && id >= 0 && id < V && y >= 0 && y < K;
+            const bool ok = i < n && 4 * (e % CH) < d && M::valid(id, labels[ic], V, K);
             rid[j] = ok ? static_cast<int32_t>(id) : -1;   // V < 2^31
         }
     };
@@ -126,17 +357,13 @@ __global__ void __launch_bounds__(NC_THREADS)
         }
     };
 
-    // Sample tid of a trip (threads below TS): its label, -1 when its id or label is out of
-    // range, -2 when the trip has no such sample.
-    int32_t my = -2;
+    // Sample tid of a trip (threads below TS): its label, marked when its id or label is out of
+    // range or when the trip has no such sample.
+    typename M::slot_t my = M::none();
     auto meta = [&](int64_t trip) {
-        my = -2;
+        my = M::none();
         const int64_t i = trip * TS + tid;
-        if (tid < TS && i < n) {
-            const int64_t id = ids[i];
-            const int32_t y = labels[i];
-            my = (id >= 0 && id < V && y >= 0 && y < K) ? y : -1;
-        }
+        if (tid < TS && i < n) my = M::slot(ids[i], labels[i], V, K);
     };
 
     // The logit pass of this wave: sample tile `sub` and k steps [st_begin, st_end) of the row's
@@ -191,11 +418,11 @@ __global__ void __launch_bounds__(NC_THREADS)
             }
         }
         if (tid < TS) {
-            if (my == -1) {
+            if (M::dropped(my)) {
                 dw::status_or(status, DW_S_BAD_INDEX);
-                if (pred) pred[trip * TS + tid] = -1;
+                if (pred) pred[trip * TS + tid] = M::DROPPED;
             }
-            s_y[tid] = my < 0 ? -1 : my;
+            sh.y[tid] = M::staged(my);
         }
         __syncthreads();
         if (trip + gridDim.x < n_trips) {   // in flight behind the trip
@@ -237,59 +464,8 @@ __global__ void __launch_bounds__(NC_THREADS)
         }
         __syncthreads();
 
-        // ---- softmax: L lanes per sample, lane j takes classes j, j + L, ...; a class's slot in
-        // part 0 of s_z is read and written by its lane alone
-        {
-            const int s = tid / L, j = tid % L;
-            const int32_t y = s_y[s];
-            double *zrow = &s_z[s * RS];
-            double m = -INFINITY, zy = 0.0;
-            int32_t arg = 0x7fffffff;
-            for (int c = j; c < K; c += L) {
-                double zc = zrow[c];
-#pragma unroll
-                for (int p = 1; p < P; ++p) zc += s_z[(p * TS + s) * RS + c];
-                zc += coef[c * ld + d];
-                zrow[c] = zc;
-                if (zc > m) {   // ascending c: the lowest class of a tie stays
-                    m = zc;
-                    arg = c;
-                }
-                if (c == y) zy = zc;
-            }
-#pragma unroll
-            for (int off = 1; off < L; off <<= 1) {
-                const double om = __shfl_xor(m, off, 64);
-                const int32_t oa = __shfl_xor(arg, off, 64);
-                if (om > m || (om == m && oa < arg)) {
-                    m = om;
-                    arg = oa;
-                }
-                zy += __shfl_xor(zy, off, 64);   // one lane's is non-zero
-            }
-            double se = 0.0;
-            for (int c = j; c < K; c += L) {
-                const double e = exp(zrow[c] - m);
-                zrow[c] = e;
-                se += e;
-            }
-#pragma unroll
-            for (int off = 1; off < L; off <<= 1) se += __shfl_xor(se, off, 64);
-            const double inv = 1.0 / se;
-#pragma unroll
-            for (int q = 0; q < S::KP / L; ++q) {
-                const int c = j + q * L;
-                double r = 0.0;
-                if (y >= 0 && c < K) r = zrow[c] * inv - (c == y ? 1.0 : 0.0);
-                zrow[c] = r;
-                sb[q] += r;   // the intercept column: a plain sum, in trip order
-            }
-            if (j == 0 && y >= 0) {
-                sum_loss += m + log(se) - zy;
-                sum_hit += arg == y ? 1.0 : 0.0;
-                if (pred) pred[trip * TS + s] = arg;
-            }
-        }
+        // ---- the per-sample stage: partial logits to residuals
+        M::template stage<S>(s_z, sh, coef, ld, d, K, tid, sb, sc, pred, trip * TS);
         __syncthreads();
 
         // ---- gradient: this wave's CT column tiles, all KT class tiles
@@ -314,7 +490,7 @@ __global__ void __launch_bounds__(NC_THREADS)
     }
 
     // ---- the block's partial row
-    const int32_t len = K * (d + 1) + 2;
+    const int32_t len = K * (d + 1) + M::tail(K);
     double *dst = partial + static_cast<int64_t>(blockIdx.x) * len;
 #pragma unroll
     for (int kt = 0; kt < KT; ++kt) {
@@ -337,33 +513,29 @@ __global__ void __launch_bounds__(NC_THREADS)
         double sum_b = 0.0;
         for (int s = 0; s < TS; ++s) sum_b += s_z[s * RS + tid];
         dst[tid * ld + d] = sum_b;
+        if constexpr (M::COUNTS) {
+            for (int w = 0; w < 3; ++w)
+                dst[K * ld + M::NSC + w * K + tid] = static_cast<double>(sh.cnt[w][tid]);
+        }
     }
-    sum_loss = dw::wave_sum_d(sum_loss);
-    sum_hit = dw::wave_sum_d(sum_hit);
-    if (lane == 0) {
-        s_sc[wave][0] = sum_loss;
-        s_sc[wave][1] = sum_hit;
+#pragma unroll
+    for (int t = 0; t < M::NSC; ++t) {
+        sc[t] = dw::wave_sum_d(sc[t]);
+        if (lane == 0) s_sc[wave][t] = sc[t];
     }
     __syncthreads();
-    if (tid < 2)
-        dst[len - 2 + tid] = ((s_sc[0][tid] + s_sc[1][tid]) + s_sc[2][tid]) + s_sc[3][tid];
+    if (tid < M::NSC)
+        dst[K * ld + tid] = ((s_sc[0][tid] + s_sc[1][tid]) + s_sc[2][tid]) + s_sc[3][tid];
 }
 
-template <int KT, int CT>
-void nc_launch(int64_t blocks, hipStream_t s, const float *table, int64_t V, int32_t d,
-               const int64_t *ids, const int32_t *labels, int64_t n, int32_t K, const double *coef,
-               double *partial, int32_t *pred, int32_t *status, int32_t vec4) {
-    hipLaunchKernelGGL((k_node_softmax<KT, CT>), dim3((unsigned)blocks), dim3(NC_THREADS), 0, s,
-                       table, V, d, ids, labels, n, K, coef, partial, pred, status, vec4);
-}
-
-template <int CT>
-void nc_launch_kt(int kt, int64_t blocks, hipStream_t s, const float *table, int64_t V, int32_t d,
-                  const int64_t *ids, const int32_t *labels, int64_t n, int32_t K,
-                  const double *coef, double *partial, int32_t *pred, int32_t *status,
-                  int32_t vec4) {
-#define DW_NC(KT_)                                                                                 \
-    nc_launch<KT_, CT>(blocks, s, table, V, d, ids, labels, n, K, coef, partial, pred, status, vec4)
+template <class M, int CT>
+void nc_launch(int kt, int64_t blocks, hipStream_t s, const float *table, int64_t V, int32_t d,
+               const int64_t *ids, const typename M::label_t *labels, int64_t n, int32_t K,
+               const double *coef, double *partial, typename M::pred_t *pred, int32_t *status,
+               int32_t vec4) {
+#define DW_NC(KT_)                                                                              \
+    hipLaunchKernelGGL((k_node_logreg<KT_, CT, M>), dim3((unsigned)blocks), dim3(NC_THREADS), 0, \
+                       s, table, V, d, ids, labels, n, K, coef, partial, pred, status, vec4)
     if (kt == 1) DW_NC(1);
     else if (kt == 2) DW_NC(2);
     else if (kt == 3) DW_NC(3);
@@ -371,13 +543,58 @@ void nc_launch_kt(int kt, int64_t blocks, hipStream_t s, const float *table, int
 #undef DW_NC
 }
 
-bool nc_sizes_ok(int64_t n, int32_t dim, int32_t n_classes) {
-    return n >= 0 && n <= INT64_MAX / 64 && dim >= 1 && dim <= 512 && n_classes >= 2 &&
+bool nc_sizes_ok(int64_t n, int32_t dim, int32_t n_classes, int32_t min_classes) {
+    return n >= 0 && n <= INT64_MAX / 64 && dim >= 1 && dim <= 512 && n_classes >= min_classes &&
            n_classes <= 64;
 }
 
-size_t nc_row_len(int32_t dim, int32_t n_classes) {
-    return static_cast<size_t>(n_classes) * (dim + 1) + 2;
+int nc_workspace_bytes(const char *what, int32_t min_classes, int32_t tail, int64_t n,
+                       int32_t dim, int32_t n_classes, size_t *bytes) {
+    DW_REQUIRE(nc_sizes_ok(n, dim, n_classes, min_classes) && bytes,
+               "%s_workspace_bytes: bad sizes (n >= 0, dim in [1, 512], n_classes in [%d, 64]; "
+               "got dim %d, n_classes %d)",
+               what, min_classes, dim, n_classes);
+    const size_t len = static_cast<size_t>(n_classes) * (dim + 1) + tail;
+    *bytes = static_cast<size_t>(nc_blocks(n, dim)) * len * sizeof(double);
+    return DW_OK;
+}
+
+// One pass under the stage M: the size checks come before the pointers, then the pass and the
+// kernel that adds the blocks' partial rows in block order.
+template <class M>
+int nc_pass(const char *what, int32_t min_classes, const float *table, int64_t vocab_size,
+            int32_t dim, const int64_t *ids, const typename M::label_t *labels, int64_t n,
+            int32_t n_classes, const double *coef, double *out, typename M::pred_t *pred,
+            void *workspace, size_t workspace_bytes, int32_t *status, void *stream) {
+    DW_REQUIRE(nc_sizes_ok(n, dim, n_classes, min_classes) && vocab_size >= 1 &&
+                   vocab_size < (int64_t(1) << 31),
+               "%s: bad sizes (vocab_size in [1, 2^31), dim in [1, 512], n_classes in [%d, 64], "
+               "n >= 0; got dim %d, n_classes %d, n %lld)",
+               what, min_classes, dim, n_classes, static_cast<long long>(n));
+    if (n == 0) return DW_OK;
+    DW_REQUIRE(table && ids && labels && coef && out && workspace, "%s: null pointer", what);
+    const int64_t blocks = nc_blocks(n, dim);
+    const size_t len = static_cast<size_t>(n_classes) * (dim + 1) + M::tail(n_classes);
+    const size_t need = static_cast<size_t>(blocks) * len * sizeof(double);
+    DW_REQUIRE(workspace_bytes >= need && reinterpret_cast<uintptr_t>(workspace) % 8 == 0,
+               "%s: workspace too small or misaligned (%zu < %zu bytes)", what, workspace_bytes,
+               need);
+    const int32_t vec4 = dim % 4 == 0 && reinterpret_cast<uintptr_t>(table) % 16 == 0;
+    const int kt = (n_classes + 15) / 16;
+    double *partial = static_cast<double *>(workspace);
+    hipStream_t s = dw::as_stream(stream);
+#define DW_NC(CT_)                                                                            \
+    nc_launch<M, CT_>(kt, blocks, s, table, vocab_size, dim, ids, labels, n, n_classes, coef, \
+                      partial, pred, status, vec4)
+    if (dim <= 128) DW_NC(2);
+    else if (dim <= 256) DW_NC(4);
+    else DW_NC(8);
+#undef DW_NC
+    DW_LAUNCH_CHECK(what);
+    hipLaunchKernelGGL(dw::k_logreg_finish, dim3((unsigned)((len + 63) / 64)), dim3(64), 0, s,
+                       partial, blocks, static_cast<int32_t>(len), out);
+    DW_LAUNCH_CHECK(what);
+    return DW_OK;
 }
 
 }  // namespace
@@ -385,48 +602,36 @@ size_t nc_row_len(int32_t dim, int32_t n_classes) {
 extern "C" {
 
 int dw_node_softmax_workspace_bytes(int64_t n, int32_t dim, int32_t n_classes, size_t *bytes) {
-    DW_REQUIRE(nc_sizes_ok(n, dim, n_classes) && bytes,
-               "dw_node_softmax_workspace_bytes: bad sizes (n >= 0, dim in [1, 512], n_classes in "
-               "[2, 64]; got dim %d, n_classes %d)",
-               dim, n_classes);
-    *bytes = static_cast<size_t>(nc_blocks(n, dim)) * nc_row_len(dim, n_classes) * sizeof(double);
-    return DW_OK;
+    return nc_workspace_bytes("dw_node_softmax", 2, NcSoftmax::tail(n_classes), n, dim, n_classes,
+                              bytes);
 }
 
 int dw_node_softmax(const float *table, int64_t vocab_size, int32_t dim, const int64_t *ids,
                     const int32_t *labels, int64_t n, int32_t n_classes, const double *coef,
                     double *out, int32_t *pred, void *workspace, size_t workspace_bytes,
                     int32_t *status, void *stream) {
-    DW_REQUIRE(nc_sizes_ok(n, dim, n_classes) && vocab_size >= 1 &&
-                   vocab_size < (int64_t(1) << 31),
-               "dw_node_softmax: bad sizes (vocab_size in [1, 2^31), dim in [1, 512], n_classes in "
-               "[2, 64], n >= 0; got dim %d, n_classes %d, n %lld)",
-               dim, n_classes, static_cast<long long>(n));
-    if (n == 0) return DW_OK;
-    DW_REQUIRE(table && ids && labels && coef && out && workspace,
-               "dw_node_softmax: null pointer");
-    const int64_t blocks = nc_blocks(n, dim);
-    const size_t len = nc_row_len(dim, n_classes);
-    const size_t need = static_cast<size_t>(blocks) * len * sizeof(double);
-    DW_REQUIRE(workspace_bytes >= need && reinterpret_cast<uintptr_t>(workspace) % 8 == 0,
-               "dw_node_softmax: workspace too small or misaligned (%zu < %zu bytes)",
-               workspace_bytes, need);
-    const int32_t vec4 = dim % 4 == 0 && reinterpret_cast<uintptr_t>(table) % 16 == 0;
-    const int kt = (n_classes + 15) / 16;
-    double *partial = static_cast<double *>(workspace);
-    hipStream_t s = dw::as_stream(stream);
-#define DW_NC(CT_)                                                                              \
-    nc_launch_kt<CT_>(kt, blocks, s, table, vocab_size, dim, ids, labels, n, n_classes, coef,   \
-                      partial, pred, status, vec4)
-    if (dim <= 128) DW_NC(2);
-    else if (dim <= 256) DW_NC(4);
-    else DW_NC(8);
-#undef DW_NC
-    DW_LAUNCH_CHECK("dw_node_softmax");
-    hipLaunchKernelGGL(dw::k_logreg_finish, dim3((unsigned)((len + 63) / 64)), dim3(64), 0, s,
-                       partial, blocks, static_cast<int32_t>(len), out);
-    DW_LAUNCH_CHECK("dw_node_softmax (finish)");
-    return DW_OK;
+    return nc_pass<NcSoftmax>("dw_node_softmax", 2, table, vocab_size, dim, ids, labels, n,
+                              n_classes, coef, out, pred, workspace, workspace_bytes, status,
+                              stream);
+}
+
+int dw_node_ovr_workspace_bytes(int64_t n, int32_t dim, int32_t n_classes, size_t *bytes) {
+    return nc_workspace_bytes("dw_node_ovr", 1, NcOvr<0>::tail(n_classes), n, dim, n_classes,
+                              bytes);
+}
+
+int dw_node_ovr(const float *table, int64_t vocab_size, int32_t dim, const int64_t *ids,
+                const uint64_t *masks, int64_t n, int32_t n_classes, const double *coef,
+                int32_t rule, double *out, uint64_t *pred, void *workspace,
+                size_t workspace_bytes, int32_t *status, void *stream) {
+    DW_REQUIRE(rule == DW_OVR_THRESHOLD || rule == DW_OVR_TOP_K,
+               "dw_node_ovr: bad rule %d (0: threshold, 1: top-k)", rule);
+    if (rule == DW_OVR_THRESHOLD)
+        return nc_pass<NcOvr<0>>("dw_node_ovr", 1, table, vocab_size, dim, ids, masks, n,
+                                 n_classes, coef, out, pred, workspace, workspace_bytes, status,
+                                 stream);
+    return nc_pass<NcOvr<1>>("dw_node_ovr", 1, table, vocab_size, dim, ids, masks, n, n_classes,
+                             coef, out, pred, workspace, workspace_bytes, status, stream);
 }
 
 }  // extern "C"

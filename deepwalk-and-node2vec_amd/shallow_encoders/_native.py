@@ -40,7 +40,10 @@ DW_EXACT_ADAM = 2
 DW_METHOD_DEEPWALK = 0
 DW_METHOD_NODE2VEC = 1
 
-ABI_VERSION = 32
+DW_OVR_THRESHOLD = 0
+DW_OVR_TOP_K = 1
+
+ABI_VERSION = 33
 
 _p = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -154,6 +157,9 @@ SIGNATURES = {
     'dw_node_softmax_workspace_bytes': (ctypes.c_int, [_i64, _i32, _i32, _szp]),
     'dw_node_softmax': (ctypes.c_int, [_p, _i64, _i32, _p, _p, _i64, _i32, _p, _p, _p, _p,
                                        ctypes.c_size_t, _p, _p]),
+    'dw_node_ovr_workspace_bytes': (ctypes.c_int, [_i64, _i32, _i32, _szp]),
+    'dw_node_ovr': (ctypes.c_int, [_p, _i64, _i32, _p, _p, _i64, _i32, _p, _i32, _p, _p, _p,
+                                   ctypes.c_size_t, _p, _p]),
     'dw_embedding_renorm_workspace_bytes': (ctypes.c_int, [_i64, _i64, _szp]),
     'dw_embedding_renorm': (ctypes.c_int, [_p, _i64, _i32, _p, _i64, _f64, _p, ctypes.c_size_t,
                                            _p, _p]),

@@ -208,11 +208,17 @@ class GraphDownstreamNodeClassificationConfig:
     # 'sklearn': the reference's host path over a float64 copy of the table; 'device': the
     # fp32 table stays in HBM (shallow_encoders/graph/nodeclf.py)
     backend: str = 'sklearn'
+    # a multi-label dataset's decision rule: 'top_k' gives a node as many labels as it truly
+    # has (the DeepWalk / node2vec papers' protocol), 'threshold' is sklearn's predict
+    prediction: str = 'top_k'
 
     def __post_init__(self):
         if self.backend not in ('sklearn', 'device'):
             raise ValueError(f'downstream.node_classification.backend must be "sklearn" or '
                              f'"device", got {self.backend!r}')
+        if self.prediction not in ('top_k', 'threshold'):
+            raise ValueError(f'downstream.node_classification.prediction must be "top_k" or '
+                             f'"threshold", got {self.prediction!r}')
 
     def instantiate_split_algorithm(self):
         """The configured split (reference: config_parser/core.py:217-232). Without one, the

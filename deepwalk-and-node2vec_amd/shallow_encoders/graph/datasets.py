@@ -276,6 +276,9 @@ class RMATDataset(RandomWalkDataset):
                          method=method, **kwargs)
 
 
+MAX_LABELS = 64   # a multi-label node's labels are one uint64 mask (dw_node_ovr)
+
+
 @register_dataset('graph_edge_list')
 class EdgeListDataset(RandomWalkDataset):
     """A user's graph from an edge-list file (graph/edge_list.py: SNAP / OGB-style text or CSV,
@@ -289,14 +292,17 @@ class EdgeListDataset(RandomWalkDataset):
     ``labels_path``: an optional node-label file (edge_list.read_node_labels; ``labels_skip_rows``
     drops its header lines). Labelled ids that are not nodes of the graph (an edge list holds no
     isolated node) are dropped and counted in ``n_labels_dropped``; nodes without a label stay
-    unlabelled.
+    unlabelled. ``multilabel``: the file is read by edge_list.read_node_label_sets instead (a node
+    may carry several labels, on one line or several) and ``label_arrays()`` gives one uint64
+    bit mask per node, so at most 64 distinct labels.
     """
 
     def __init__(self, walks_per_node: int, walk_length: int, method: str = 'deepwalk',
                  path: Optional[str] = None, skip_rows: int = 0, build: str = 'auto',
                  labels_path: Optional[str] = None, labels_skip_rows: int = 0,
-                 weighted: bool = False, **kwargs):
-        from shallow_encoders.graph.edge_list import read_edge_list, read_node_labels
+                 weighted: bool = False, multilabel: bool = False, **kwargs):
+        from shallow_encoders.graph.edge_list import (read_edge_list, read_node_label_sets,
+                                                      read_node_labels)
         if path is None:
             raise ValueError('graph_edge_list needs the edge-list file: set '
                              'datamodule.additional_parameters.path=<file>')
@@ -309,8 +315,10 @@ class EdgeListDataset(RandomWalkDataset):
         self._label_arrays = None
         self._label_dict = None
         self.n_labels_dropped = 0
+        self._multilabel = bool(multilabel)
         if labels_path is not None:
-            ids, tokens = read_node_labels(os.path.expanduser(labels_path), labels_skip_rows)
+            read = read_node_label_sets if self.is_multilabel else read_node_labels
+            ids, tokens = read(os.path.expanduser(labels_path), labels_skip_rows)
             node_ids = graph.itos.ids
             pos = np.minimum(np.searchsorted(node_ids, ids), len(node_ids) - 1)
             keep = np.flatnonzero(node_ids[pos] == ids)
@@ -319,11 +327,21 @@ class EdgeListDataset(RandomWalkDataset):
                 logger.info(f'{labels_path}: dropped {self.n_labels_dropped} labelled ids that '
                             f'are not nodes of the graph.')
             keep = keep[np.argsort(pos[keep], kind='stable')]
-            classes = sorted({tokens[k] for k in keep})
-            rank = {c: i for i, c in enumerate(classes)}
-            self._label_arrays = (
-                (pos[keep] + 1).astype(np.int64),
-                np.asarray([rank[tokens[k]] for k in keep], dtype=np.int32), classes)
+            rows = (pos[keep] + 1).astype(np.int64)
+            if self.is_multilabel:
+                classes = sorted({t for k in keep for t in tokens[k]})
+                if len(classes) > MAX_LABELS:
+                    raise ValueError(f'{labels_path}: {len(classes)} distinct labels; a '
+                                     f'multi-label mask holds at most {MAX_LABELS}')
+                rank = {c: i for i, c in enumerate(classes)}
+                masks = np.asarray([sum(1 << rank[t] for t in tokens[k]) for k in keep],
+                                   dtype=np.uint64).view(np.int64)
+                self._label_arrays = (rows, masks, classes)
+            else:
+                classes = sorted({tokens[k] for k in keep})
+                rank = {c: i for i, c in enumerate(classes)}
+                self._label_arrays = (
+                    rows, np.asarray([rank[tokens[k]] for k in keep], dtype=np.int32), classes)
         super().__init__(graph=graph, walks_per_node=walks_per_node, walk_length=walk_length,
                          method=method, **kwargs)
 
@@ -332,19 +350,30 @@ class EdgeListDataset(RandomWalkDataset):
         return self._label_arrays is not None
 
     @property
+    def is_multilabel(self) -> bool:
+        return self._multilabel
+
+    @property
     def labels(self) -> Dict[str, str]:
         """The reference's ``{node name: label token}`` over the labelled nodes only, built on
-        first use from the graph's names."""
+        first use from the graph's names. Multi-label: a tuple of the node's tokens, sorted."""
         assert self.has_labels, 'This dataset does not have any labels!'
         if self._label_dict is None:
             rows, y, classes = self._label_arrays
             names = self.csr.itos
-            self._label_dict = {names[int(r)]: classes[int(c)] for r, c in zip(rows, y)}
+            if self.is_multilabel:
+                self._label_dict = {
+                    names[int(r)]: tuple(c for i, c in enumerate(classes) if int(m) >> i & 1)
+                    for r, m in zip(rows, y.view(np.uint64))}
+            else:
+                self._label_dict = {names[int(r)]: classes[int(c)] for r, c in zip(rows, y)}
         return self._label_dict
 
     def label_arrays(self):
         """(rows int64[n], y int32[n], classes list[str]): the labelled nodes' vocabulary ids,
         ascending and never 0, and each one's class — the rank of its token among the sorted
-        distinct tokens (the numbering ``labels_to_integers`` gives the dict form)."""
+        distinct tokens (the numbering ``labels_to_integers`` gives the dict form). Multi-label:
+        instead of y, masks int64[n] that hold uint64 bit patterns, bit c set when the node has
+        the c-th of the sorted distinct tokens."""
         assert self.has_labels, 'This dataset does not have any labels!'
         return self._label_arrays

@@ -46,6 +46,10 @@ Node labels (``read_node_labels``) come in a file of their own, one line per nod
 line rules: optional blanks, the node's id (1-18 digits), one or more separators, the label token
 (a run of bytes other than the separators and line ends), then the end of the line or a separator
 followed by anything. An id that appears twice is a ``ValueError`` naming its second line.
+
+Multi-label files (``read_node_label_sets``, e.g. BlogCatalog's ``group-edges.csv``) follow the
+same line rules, except that every token after the id is a label (``node l1 [l2 ...]``) and a node
+may appear on several lines: its labels are unioned.
 """
 import os
 import re
@@ -464,6 +468,24 @@ def read_edge_list(path: str, device=None, skip_rows: int = 0,
 _LABEL_LINE = re.compile(rb'([0-9]{1,18})[ \t,]+([^ \t,\r\n]+)(?:[ \t,]|\Z)')
 
 
+def _label_lines(path: str, skip_rows: int):
+    """(index, line without its line end, the line without leading blanks) of a label file's
+    lines that hold data: not skipped, not blank, no comment."""
+    with open(path, 'rb') as f:
+        lines = f.read().split(b'\n')
+    if lines and lines[-1] == b'':
+        lines.pop()
+    for k, line in enumerate(lines):
+        if k < skip_rows:
+            continue
+        if line.endswith(b'\r'):
+            line = line[:-1]
+        t = line.lstrip(b' \t')
+        if not t or t[:1] in (b'#', b'%'):
+            continue
+        yield k, line, t
+
+
 def read_node_labels(path: str, skip_rows: int = 0) -> Tuple[np.ndarray, List[str]]:
     """(ids int64[m], tokens list[str]) of a node-label file, in file order: ``.npz`` (integer
     arrays ``node`` and ``label``; the labels' decimal strings are the tokens), anything else as
@@ -484,21 +506,10 @@ def read_node_labels(path: str, skip_rows: int = 0) -> Tuple[np.ndarray, List[st
             raise ValueError(f'{path}: node {int(ids[second])} is labelled twice (entry '
                              f'{second + 1})')
         return ids, [str(int(v)) for v in label]
-    with open(path, 'rb') as f:
-        lines = f.read().split(b'\n')
-    if lines and lines[-1] == b'':
-        lines.pop()
     ids: List[int] = []
     tokens: List[str] = []
     seen = set()
-    for k, line in enumerate(lines):
-        if k < skip_rows:
-            continue
-        if line.endswith(b'\r'):
-            line = line[:-1]
-        t = line.lstrip(b' \t')
-        if not t or t[:1] in (b'#', b'%'):
-            continue
+    for k, line, t in _label_lines(path, skip_rows):
         m = _LABEL_LINE.match(t)
         if m is None:
             raise ValueError(f'{path}: line {k + 1} is not a node label: '
@@ -510,3 +521,36 @@ def read_node_labels(path: str, skip_rows: int = 0) -> Tuple[np.ndarray, List[st
         ids.append(node)
         tokens.append(m.group(2).decode(errors='replace'))
     return np.asarray(ids, dtype=np.int64), tokens
+
+
+_LABEL_SET_LINE = re.compile(rb'([0-9]{1,18})((?:[ \t,]+[^ \t,\r\n]+)+)[ \t,]*\Z')
+
+
+def read_node_label_sets(path: str, skip_rows: int = 0) -> Tuple[np.ndarray, List[List[str]]]:
+    """(ids int64[m], label tokens of each id) of a multi-label file: the distinct ids in order
+    of first appearance, each with its distinct tokens in order of first appearance. ``.npz``
+    (integer arrays ``node`` and ``label``, one entry per (node, label) pair), anything else as
+    text lines ``node l1 [l2 ...]`` (module docstring). A node may be named on several lines or
+    entries; a repeated pair counts once."""
+    path = os.fspath(path)
+    if skip_rows < 0:
+        raise ValueError('skip_rows must be non-negative')
+    sets = {}
+    if os.path.splitext(path)[1].lower() == '.npz':
+        with np.load(path, allow_pickle=False) as f:
+            node, label = np.asarray(f['node']), np.asarray(f['label'])
+        if node.ndim != 1 or node.shape != label.shape or node.dtype.kind not in 'iu' \
+                or label.dtype.kind not in 'iu':
+            raise ValueError(f'{path}: node and label must be 1-d integer arrays of one length')
+        for u, v in zip(_host_ids(node, 'node').tolist(), label.tolist()):
+            sets.setdefault(u, {})[str(v)] = None
+    else:
+        for k, line, t in _label_lines(path, skip_rows):
+            m = _LABEL_SET_LINE.match(t)
+            if m is None:
+                raise ValueError(f'{path}: line {k + 1} is not a node and its labels: '
+                                 f'{line[:60].decode(errors="replace")!r}')
+            mine = sets.setdefault(int(m.group(1)), {})
+            for token in re.split(rb'[ \t,]+', m.group(2).strip(b' \t,')):
+                mine[token.decode(errors='replace')] = None
+    return np.asarray(list(sets), dtype=np.int64), [list(v) for v in sets.values()]

@@ -20,7 +20,9 @@ non-neighbours (itself included). sklearn's LogisticRegression with the config's
 (shallow_encoders/graph/linkpred.py: the graph's CSR, so ``graph_rmat`` datasets work too) or
 ``downstream.node_classification.backend=device`` the one for the node task
 (shallow_encoders/graph/nodeclf.py: the fp32 table stays on the GPU; embeddings only, no node
-features, no 2-D plot; macro-F1 is logged beside the accuracy).
+features, no 2-D plot; macro-F1 is logged beside the accuracy). A multi-label dataset
+(``graph_edge_list`` with ``multilabel=true``) runs on the device backend only: one-vs-rest
+logistic regression, micro- and macro-F1 under ``downstream.node_classification.prediction``.
 Only the labelled vertices are classified: a ``graph_edge_list`` dataset's label file may cover
 a part of the nodes.
 """
@@ -92,6 +94,17 @@ def node_classification(embeddings: np.ndarray, itos: List[str], labels: Dict[st
     return mean, best
 
 
+def is_multilabel(dataset) -> bool:
+    return bool(getattr(getattr(dataset, 'dataset', dataset), 'is_multilabel', False))
+
+
+def check_node_backend(dataset, nc) -> None:
+    """The host path fits one label per node: a multi-label dataset needs the device backend."""
+    if nc.backend != 'device' and is_multilabel(dataset):
+        raise ValueError('a multi-label dataset is classified on the device only: set '
+                         'downstream.node_classification.backend=device')
+
+
 def node_classification_on_device(embeddings: np.ndarray, dataset, nc) -> Dict[str, float]:
     """``backend: device``: the same protocol with the table and the logistic regression on the
     GPU (shallow_encoders/graph/nodeclf.py). The labelled rows come from the dataset's
@@ -103,6 +116,17 @@ def node_classification_on_device(embeddings: np.ndarray, dataset, nc) -> Dict[s
         raise ValueError('downstream.node_classification.backend=device classifies the '
                          'embeddings alone: this dataset has node features (use backend=sklearn)')
     inner = getattr(dataset, 'dataset', dataset)
+    if is_multilabel(dataset):
+        rows, masks, classes = inner.label_arrays()
+        logger.info(f'Dataset info: {len(rows)} labelled nodes, {len(classes)} labels, '
+                    f'd={embeddings.shape[1]}.')
+        dev = _native.require_device(None)
+        table = torch.from_numpy(np.ascontiguousarray(embeddings, dtype=np.float32)).to(dev)
+        micro, macro, best = nodeclf.node_multilabel_device(
+            table, rows, masks, nc.instantiate_split_algorithm(), nc.n_experiments,
+            classifier_params=nc.classifier_params, rule=nc.prediction, device=dev,
+            n_classes=len(classes))
+        return {'node_micro_f1': micro, 'node_macro_f1': macro, 'node_best_micro_f1': best}
     if hasattr(inner, 'label_arrays'):
         rows, y, _ = inner.label_arrays()
     else:
@@ -254,6 +278,8 @@ def main(argv=None) -> Dict[str, float]:
     Path(analysis_dir).mkdir(parents=True, exist_ok=True)
     result: Dict[str, float] = {}
     nc = cfg.downstream.node_classification
+    if nc.enable:
+        check_node_backend(dataset, nc)
     if nc.enable and nc.backend == 'device':
         result.update(node_classification_on_device(emb, dataset, nc))
     elif nc.enable:

@@ -850,6 +850,29 @@ int dw_node_softmax(const float *table, int64_t vocab_size, int32_t dim, const i
                     double *out, int32_t *pred, void *workspace, size_t workspace_bytes,
                     int32_t *status, void *stream);
 
+/* One pass of a one-vs-rest logistic regression over the rows table[ids[i]]: the multi-label
+ * sibling of dw_node_softmax (a departure: the reference has no multi-label task), same staging,
+ * same two float64 MFMA products, same accumulation order. masks uint64[n]: bit c of masks[i]
+ * says sample i has label c; mask 0 is a valid sample of no label. 1 <= n_classes <= 64. A
+ * sample whose id is outside [0, vocab_size) or whose mask has a bit at or above n_classes sets
+ * DW_S_BAD_INDEX, contributes nothing to any sum and gets pred 0. Per sample and class c, with
+ * y_c the mask's bit: z_c = w_c . x + b_c, loss = max(z_c, 0) - y_c z_c + log1p(exp(-|z_c|)),
+ * r_c = sigmoid(z_c) - y_c, the sigmoid from exp(-|z_c|) (finite for every z). Predicted labels:
+ * rule DW_OVR_THRESHOLD, every c with z_c > 0; rule DW_OVR_TOP_K, with k = popcount(masks[i]),
+ * every c whose rank #{c' : z_c' > z_c, or z_c' = z_c and c' < c} is below k (ties to the lowest
+ * class, k = 0 predicts nothing). pred uint64[n] (or NULL; the sums do not depend on it) receives
+ * them as a mask. out double[K (dim + 1) + 1 + 3 K], K = n_classes:
+ * [c * (dim + 1) + j] = sum r_c x_j for j < dim and sum r_c at j = dim, then the summed loss,
+ * then tp[K] (samples with label c that are predicted c), predicted[K] and true[K], exact
+ * integers. Reproducible bit for bit as dw_node_softmax is, the counts by integer adds. */
+#define DW_OVR_THRESHOLD 0
+#define DW_OVR_TOP_K 1
+int dw_node_ovr_workspace_bytes(int64_t n, int32_t dim, int32_t n_classes, size_t *bytes);
+int dw_node_ovr(const float *table, int64_t vocab_size, int32_t dim, const int64_t *ids,
+                const uint64_t *masks, int64_t n, int32_t n_classes, const double *coef,
+                int32_t rule, double *out, uint64_t *pred, void *workspace,
+                size_t workspace_bytes, int32_t *status, void *stream);
+
 /* nn.Embedding(max_norm=...) lookup side effect (model.py:24-25 with max_norm set; torch
  * embedding_renorm_): every DISTINCT row among ids[0..n_ids) whose L2 norm exceeds max_norm is
  * scaled by max_norm / (norm + 1e-7), in place. Ids are deduplicated on the device (radix sort

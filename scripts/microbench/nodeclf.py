@@ -8,10 +8,14 @@ pass's cost does not depend on the data.
               device events, after a warm-up window) for (dim, K) in SHAPES; its MFMA FLOP/s
               (4 n Kp dim with Kp = K rounded up to 16: what the instruction stream executes)
               as a fraction of the yardstick, and the useful share 4 n K dim;
+  ovr         dw_node_ovr under both decision rules beside dw_node_softmax at the same shape,
+              SHAPES plus (128, 39) (BlogCatalog's label count): windows of the three alternate
+              in one process; ms per pass (medians), each rule's ratio to softmax and the
+              softmax windows' spread, (max - min) / median — the yardstick of the ratios;
   fit         the wall time of one whole NodeLogisticRegression.fit at (128, 7);
   sklearn     LogisticRegression().fit on the float64 copy of the same features, 16 threads.
 
-    python scripts/microbench/nodeclf.py [--json PATH] [--part all|yardstick|pass|fit|sklearn]
+    python scripts/microbench/nodeclf.py [--json PATH] [--part all|yardstick|pass|ovr|fit|sklearn]
 
 Without --part every part runs in a process of its own under `timeout`, one after the other, and
 the run stops at the first that fails. One JSON line per record on stdout (and appended to
@@ -96,6 +100,51 @@ def part_pass(path, reps, peak):
         del table, ids, labels, ws, pred
 
 
+def part_ovr(path, reps):
+    import torch
+    from shallow_encoders.graph import nodeclf
+    dev = torch.device('cuda', 0)
+    for d, K in SHAPES + ((128, 39),):
+        table, ids, labels = problem(d, K, dev)
+        # about two labels a sample, as bit masks; bit 63 is never set at these K
+        bits = torch.rand((N, K), device=dev) < min(2.0 / K, 0.5)
+        masks = (bits.to(torch.int64) << torch.arange(K, device=dev)).sum(dim=1)
+        del bits
+        coef = (torch.randn((K, d + 1), dtype=torch.float64, device=dev) / d ** 0.5).contiguous()
+        ws = nodeclf.ovr_workspace(N, d, K, dev)   # the longer row: serves softmax too
+        pred32 = torch.empty(N, dtype=torch.int32, device=dev)
+        pred64 = torch.empty(N, dtype=torch.int64, device=dev)
+        runs = {
+            'softmax': lambda: nodeclf.softmax_sums(table, ids, labels, coef, K, ws, pred=pred32,
+                                                    check=False),
+            'threshold': lambda: nodeclf.ovr_sums(table, ids, masks, coef, K, 'threshold', ws,
+                                                  pred=pred64, check=False),
+            'top_k': lambda: nodeclf.ovr_sums(table, ids, masks, coef, K, 'top_k', ws,
+                                              pred=pred64, check=False)}
+
+        def window(run):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(reps):
+                run()
+            b.record()
+            torch.cuda.synchronize(dev)
+            return a.elapsed_time(b) / reps
+        for run in runs.values():   # warm-up
+            window(run)
+        ms = {name: [] for name in runs}
+        for _ in range(WINDOWS):   # alternating: drift on a shared box hits all three alike
+            for name, run in runs.items():
+                ms[name].append(window(run))
+        med = {name: statistics.median(v) for name, v in ms.items()}
+        emit({'part': 'ovr', 'd': d, 'K': K, 'samples': N, 'ms_per_pass': med, 'ms_windows': ms,
+              'ratio_to_softmax': {name: med[name] / med['softmax']
+                                   for name in ('threshold', 'top_k')},
+              'softmax_spread': (max(ms['softmax']) - min(ms['softmax'])) / med['softmax']},
+             path)
+        del table, ids, labels, masks, ws, pred32, pred64
+
+
 def part_fit(path, d=128, K=7):
     import torch
     from shallow_encoders.graph import nodeclf
@@ -131,7 +180,8 @@ def part_sklearn(path, d=128, K=7):
 def run_all(args):
     """Every part in a process of its own under `timeout`; stops at the first failure."""
     peak = None
-    for part, limit in (('yardstick', 120), ('pass', 300), ('fit', 300), ('sklearn', 400)):
+    for part, limit in (('yardstick', 120), ('pass', 300), ('ovr', 300), ('fit', 300),
+                        ('sklearn', 400)):
         cmd = ['timeout', '-k', '10', str(limit), sys.executable, os.path.abspath(__file__),
                '--part', part, '--reps', str(args.reps)]
         if args.json:
@@ -153,7 +203,7 @@ def run_all(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--part', default='all',
-                    choices=['all', 'yardstick', 'pass', 'fit', 'sklearn'])
+                    choices=['all', 'yardstick', 'pass', 'ovr', 'fit', 'sklearn'])
     ap.add_argument('--json', default=None)
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--peak', type=float, default=None, help='the yardstick\'s FLOP/s')
@@ -164,6 +214,8 @@ def main():
         part_yardstick(args.json)
     elif args.part == 'pass':
         part_pass(args.json, args.reps, args.peak)
+    elif args.part == 'ovr':
+        part_ovr(args.json, args.reps)
     elif args.part == 'fit':
         part_fit(args.json)
     else:
