@@ -7,11 +7,16 @@
 // operator(n1, n2) feature matrices (graph/edge_operators.py) and fits sklearn's logistic
 // regression on them. Here the draw is one Philox call and one binary search of u's sorted row
 // (the k-th non-neighbour by rank, no rejection), and the regression's loss, gradient and
-// accuracy over n pairs are one gather pass that never stores a feature.
+// accuracy over n pairs are one gather pass that never stores a feature. For held-out link
+// prediction the same pass writes each pair's score instead (dw_edge_scores),
+// and dw_roc_auc turns scores and labels into the exact integer Mann-Whitney count.
 //
 // Compiled with -ffp-contract=off (csrc/build.py): the fp32 operator expressions round exactly
 // as written, so dw_edge_features equals numpy float32 bit for bit.
+#include <rocprim/device/device_radix_sort.hpp>
+
 #include "dw_common.h"
+#include "dw_ingest.h"
 
 namespace {
 
@@ -154,7 +159,10 @@ __host__ __device__ inline int64_t logreg_blocks(int64_t n, int groups_per_block
     return b < 1 ? 1 : b;
 }
 
-template <int VEC, int G, int C>
+// SCORES (dw_edge_scores): the same gather, operator and float64 dot product, and then z itself
+// goes to partial[sample] — no label, loss, gradient or sum across samples; a null coef means
+// unit weights and a zero intercept.
+template <int VEC, int G, int C, bool SCORES = false>
 __global__ void __launch_bounds__(256)
     k_edge_logreg(const float *__restrict__ table, int64_t V, int32_t d, int32_t op,
                   const int64_t *__restrict__ pairs, const uint8_t *__restrict__ labels,
@@ -182,9 +190,10 @@ __global__ void __launch_bounds__(256)
         const int e0 = (c * G + gl) * VEC;
         live[c] = e0 < d;
 #pragma unroll
-        for (int k = 0; k < VEC; ++k) w[c * VEC + k] = live[c] ? coef[e0 + k] : 0.0;
+        for (int k = 0; k < VEC; ++k)
+            w[c * VEC + k] = live[c] ? (SCORES && !coef ? 1.0 : coef[e0 + k]) : 0.0;
     }
-    const double b0 = coef[d];
+    const double b0 = SCORES && !coef ? 0.0 : coef[d];
 
     double acc[E];
 #pragma unroll
@@ -209,7 +218,7 @@ __global__ void __launch_bounds__(256)
                 const int64_t p0 = pairs[2 * s], p1 = pairs[2 * s + 1];
                 const bool ok = p0 >= 0 && p0 < V && p1 >= 0 && p1 < V;
                 t.flags |= (1u << u) | (ok ? 1u << (8 + u) : 0u) |
-                           (labels[s] != 0 ? 1u << (16 + u) : 0u);
+                           (!SCORES && labels[s] != 0 ? 1u << (16 + u) : 0u);
                 if (ok) {   // V < 2^31
                     t.a[u] = static_cast<int32_t>(p0);
                     t.b[u] = static_cast<int32_t>(p1);
@@ -305,6 +314,10 @@ __global__ void __launch_bounds__(256)
         for (int off = 4; off < G; off <<= 1) zs += __shfl_xor(zs, off, 64);
         zs += b0;
         const bool vs = ((flags >> mine) & 1u) != 0;
+        if constexpr (SCORES) {
+            if (gl < U && vs) partial[base + mine] = zs;
+            continue;
+        }
         const double ys = ((flags >> (16 + mine)) & 1u) ? 1.0 : 0.0;
         const double e = exp(-fabs(zs));
         const double inv = 1.0 / (1.0 + e);
@@ -324,6 +337,7 @@ __global__ void __launch_bounds__(256)
         }
     }
 
+    if constexpr (SCORES) return;
     // the block's sums: groups in group order, then the waves' scalars in wave order
     for (int i = threadIdx.x; i < 512; i += 256) s_sum[i] = 0.0;
     __syncthreads();
@@ -357,12 +371,12 @@ __global__ void __launch_bounds__(256)
     }
 }
 
-template <int VEC, int G, int C>
+template <int VEC, int G, int C, bool SCORES>
 void logreg_launch(int64_t blocks, hipStream_t s, const float *table, int64_t V, int32_t d,
                    int32_t op, const int64_t *pairs, const uint8_t *labels, int64_t n,
                    const double *coef, double *partial, int32_t *status) {
-    hipLaunchKernelGGL((k_edge_logreg<VEC, G, C>), dim3((unsigned)blocks), dim3(256), 0, s, table,
-                       V, d, op, pairs, labels, n, coef, partial, status);
+    hipLaunchKernelGGL((k_edge_logreg<VEC, G, C, SCORES>), dim3((unsigned)blocks), dim3(256), 0, s,
+                       table, V, d, op, pairs, labels, n, coef, partial, status);
 }
 
 // The launch shape of (d, 16-B rows or not): lanes per sample G, chunks per lane C.
@@ -382,9 +396,130 @@ LogregShape logreg_shape(int32_t d, bool vec4) {
     return {1, 64, c <= 1 ? 1 : c <= 2 ? 2 : c <= 4 ? 4 : 8};
 }
 
+// One launch of the (d, alignment) shape's instantiation: the logreg pass or the scores pass.
+template <bool SCORES>
+void logreg_dispatch(const LogregShape &sh, int64_t blocks, hipStream_t s, const float *table,
+                     int64_t V, int32_t d, int32_t op, const int64_t *pairs,
+                     const uint8_t *labels, int64_t n, const double *coef, double *partial,
+                     int32_t *status) {
+#define DW_LR(V_, G_, C_)                                                                       \
+    logreg_launch<V_, G_, C_, SCORES>(blocks, s, table, V, d, op, pairs, labels, n, coef,       \
+                                      partial, status)
+    if (sh.vec == 4) {
+        if (sh.G == 16) DW_LR(4, 16, 1);
+        else if (sh.G == 32) DW_LR(4, 32, 1);
+        else if (sh.C == 1) DW_LR(4, 64, 1);
+        else DW_LR(4, 64, 2);
+    } else {
+        if (sh.C == 1) DW_LR(1, 64, 1);
+        else if (sh.C == 2) DW_LR(1, 64, 2);
+        else if (sh.C == 4) DW_LR(1, 64, 4);
+        else DW_LR(1, 64, 8);
+    }
+#undef DW_LR
+}
+
 bool sizes_ok(int64_t vocab_size, int32_t dim, int32_t op, int64_t n) {
     return vocab_size >= 1 && vocab_size < (int64_t(1) << 31) && dim >= 1 && dim <= 512 &&
            op >= 0 && op <= 3 && n >= 0;
+}
+
+// ---- dw_roc_auc ------------------------------------------------------------------------------
+// The tie-aware Mann-Whitney count as an integer: U2 = sum over positives i of
+// 2 #{negatives j: s_j < s_i} + #{negatives j: s_j = s_i}. A score becomes a uint64 key of the
+// same order (-0.0 and +0.0 tie); the negatives' keys are sorted with every positive's slot
+// holding AUC_PAD, which is above every key of a number (+inf is 0xFFF0...0), so the sorted array
+// is the n_neg negatives followed by padding and the sort's length does not depend on a count
+// the host would have to read first. A positive's lower bound lb and upper bound ub in it are
+// the two counts: its term is lb + ub. Integer sums: one 64-bit atomic per block and counter,
+// the same result in any order.
+constexpr uint64_t AUC_PAD = ~uint64_t(0);
+constexpr int AUC_MAX_BLOCKS = 2048;   // 256 CUs x 8 blocks; the loop strides over the rest
+
+__device__ __forceinline__ uint64_t score_key(double s) {
+    const uint64_t b = static_cast<uint64_t>(__double_as_longlong(s == 0.0 ? 0.0 : s));
+    return (b >> 63) ? ~b : b | (uint64_t(1) << 63);
+}
+
+__global__ void __launch_bounds__(256)
+    k_auc_keys(const double *__restrict__ scores, const uint8_t *__restrict__ labels, int64_t n,
+               uint64_t *__restrict__ keys, int32_t *status) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += stride) {
+        const double s = scores[i];
+        if (s != s) dw::status_or(status, DW_S_NAN_SCORE);
+        keys[i] = labels[i] != 0 ? AUC_PAD : score_key(s);
+    }
+}
+
+__global__ void __launch_bounds__(256)
+    k_auc_terms(const double *__restrict__ scores, const uint8_t *__restrict__ labels, int64_t n,
+                const uint64_t *__restrict__ sorted, unsigned long long *out) {
+    __shared__ unsigned long long s_part[4][3];
+    unsigned long long u2 = 0, n_pos = 0, n_neg = 0;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += stride) {
+        if (labels[i] == 0) {
+            ++n_neg;
+            continue;
+        }
+        ++n_pos;
+        const uint64_t k = score_key(scores[i]);
+        int64_t lo = 0, hi = n;   // lb: the first index whose key is >= k
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (sorted[mid] < k)
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        const int64_t lb = lo;
+        hi = n;                   // ub: the first index whose key is > k
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (sorted[mid] <= k)
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        u2 += static_cast<unsigned long long>(lb + lo);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        u2 += __shfl_xor(u2, off, 64);
+        n_pos += __shfl_xor(n_pos, off, 64);
+        n_neg += __shfl_xor(n_neg, off, 64);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        s_part[wave][0] = u2;
+        s_part[wave][1] = n_pos;
+        s_part[wave][2] = n_neg;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int k = threadIdx.x;
+        const unsigned long long t = s_part[0][k] + s_part[1][k] + s_part[2][k] + s_part[3][k];
+        if (t) atomicAdd(out + k, t);
+    }
+}
+
+struct AucBufs {
+    uint64_t *keys0, *keys1;
+    void *tmp;
+    size_t tmp_bytes;
+};
+
+int plan_auc(dw::Arena &a, int64_t n, AucBufs *p) {
+    const size_t m = static_cast<size_t>(n > 0 ? n : 1);
+    rocprim::double_buffer<uint64_t> kb(nullptr, nullptr);
+    p->tmp_bytes = 0;
+    DW_HIP_OK(rocprim::radix_sort_keys(nullptr, p->tmp_bytes, kb, m, 0, 64),
+              "dw_roc_auc: sort plan");
+    p->keys0 = a.take<uint64_t>(m);
+    p->keys1 = a.take<uint64_t>(m);
+    p->tmp = a.take<char>(p->tmp_bytes);
+    return DW_OK;
 }
 
 }  // namespace
@@ -463,26 +598,73 @@ int dw_edge_logreg(const float *table, int64_t vocab_size, int32_t dim, int32_t 
                workspace_bytes, need);
     double *partial = static_cast<double *>(workspace);
     hipStream_t s = dw::as_stream(stream);
-#define DW_LR(V_, G_, C_)                                                                       \
-    logreg_launch<V_, G_, C_>(blocks, s, table, vocab_size, dim, op, pairs, labels, n, coef,    \
-                              partial, status)
-    if (sh.vec == 4) {
-        if (sh.G == 16) DW_LR(4, 16, 1);
-        else if (sh.G == 32) DW_LR(4, 32, 1);
-        else if (sh.C == 1) DW_LR(4, 64, 1);
-        else DW_LR(4, 64, 2);
-    } else {
-        if (sh.C == 1) DW_LR(1, 64, 1);
-        else if (sh.C == 2) DW_LR(1, 64, 2);
-        else if (sh.C == 4) DW_LR(1, 64, 4);
-        else DW_LR(1, 64, 8);
-    }
-#undef DW_LR
+    logreg_dispatch<false>(sh, blocks, s, table, vocab_size, dim, op, pairs, labels, n, coef, partial,
+                           status);
     DW_LAUNCH_CHECK("dw_edge_logreg");
     const int32_t len = dim + 3;
     hipLaunchKernelGGL(dw::k_logreg_finish, dim3((unsigned)((len + 63) / 64)), dim3(64), 0, s, partial,
                        blocks, len, out);
     DW_LAUNCH_CHECK("dw_edge_logreg (finish)");
+    return DW_OK;
+}
+
+int dw_edge_scores(const float *table, int64_t vocab_size, int32_t dim, int32_t op,
+                   const int64_t *pairs, int64_t n, const double *coef, double *z_out,
+                   int32_t *status, void *stream) {
+    DW_REQUIRE(sizes_ok(vocab_size, dim, op, n),
+               "dw_edge_scores: bad sizes (vocab_size in [1, 2^31), dim in [1, 512], op in "
+               "[0, 3], n >= 0; got dim %d, op %d, n %lld)",
+               dim, op, static_cast<long long>(n));
+    DW_REQUIRE(n <= INT64_MAX / 8, "dw_edge_scores: n too large");
+    if (n == 0) return DW_OK;
+    DW_REQUIRE(table && pairs && z_out, "dw_edge_scores: null pointer");
+    const bool vec4 = dim % 4 == 0 && reinterpret_cast<uintptr_t>(table) % 16 == 0;
+    const LogregShape sh = logreg_shape(dim, vec4);
+    const int64_t blocks = logreg_blocks(n, 4 * (64 / sh.G));
+    logreg_dispatch<true>(sh, blocks, dw::as_stream(stream), table, vocab_size, dim, op, pairs,
+                          nullptr, n, coef, z_out, status);
+    DW_LAUNCH_CHECK("dw_edge_scores");
+    return DW_OK;
+}
+
+int dw_roc_auc_workspace_bytes(int64_t n, size_t *bytes) {
+    DW_REQUIRE(n >= 0 && n < (int64_t(1) << 31) && bytes,
+               "dw_roc_auc_workspace_bytes: n must be in [0, 2^31)");
+    dw::Arena a{nullptr};
+    AucBufs p;
+    const int rc = plan_auc(a, n, &p);
+    if (rc != DW_OK) return rc;
+    *bytes = a.off;
+    return DW_OK;
+}
+
+int dw_roc_auc(const double *scores, const uint8_t *labels, int64_t n, int64_t *out,
+               int32_t *status, void *workspace, size_t workspace_bytes, void *stream) {
+    DW_REQUIRE(n >= 0 && n < (int64_t(1) << 31), "dw_roc_auc: n must be in [0, 2^31)");
+    DW_REQUIRE(out && status, "dw_roc_auc: null pointer");
+    hipStream_t st = dw::as_stream(stream);
+    DW_HIP_OK(hipMemsetAsync(out, 0, 3 * sizeof(int64_t), st), "dw_roc_auc: memset");
+    if (n == 0) return DW_OK;
+    DW_REQUIRE(scores && labels && workspace, "dw_roc_auc: null pointer");
+    dw::Arena a{static_cast<char *>(workspace)};
+    AucBufs p;
+    const int rc = plan_auc(a, n, &p);
+    if (rc != DW_OK) return rc;
+    DW_REQUIRE(workspace_bytes >= a.off && reinterpret_cast<uintptr_t>(workspace) % 256 == 0,
+               "dw_roc_auc: workspace too small or misaligned (%zu < %zu bytes)",
+               workspace_bytes, a.off);
+    int64_t blocks = (n + 255) / 256;
+    if (blocks > AUC_MAX_BLOCKS) blocks = AUC_MAX_BLOCKS;
+    hipLaunchKernelGGL(k_auc_keys, dim3((unsigned)blocks), dim3(256), 0, st, scores, labels, n,
+                       p.keys0, status);
+    DW_LAUNCH_CHECK("dw_roc_auc/keys");
+    rocprim::double_buffer<uint64_t> kb(p.keys0, p.keys1);
+    size_t tmp_bytes = p.tmp_bytes;
+    DW_HIP_OK(rocprim::radix_sort_keys(p.tmp, tmp_bytes, kb, static_cast<size_t>(n), 0, 64, st),
+              "dw_roc_auc: sort");
+    hipLaunchKernelGGL(k_auc_terms, dim3((unsigned)blocks), dim3(256), 0, st, scores, labels, n,
+                       kb.current(), reinterpret_cast<unsigned long long *>(out));
+    DW_LAUNCH_CHECK("dw_roc_auc/terms");
     return DW_OK;
 }
 

@@ -34,6 +34,7 @@ DW_S_DUP_NEIGHBOR = 64
 DW_S_FIXED_RANGE = 128
 DW_S_BAD_TEXT = 256
 DW_S_NEG_WEIGHT = 512
+DW_S_NAN_SCORE = 1024
 DW_EXACT_DEFER = 1
 DW_EXACT_ADAM = 2
 
@@ -43,7 +44,7 @@ DW_METHOD_NODE2VEC = 1
 DW_OVR_THRESHOLD = 0
 DW_OVR_TOP_K = 1
 
-ABI_VERSION = 33
+ABI_VERSION = 34
 
 _p = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -154,6 +155,14 @@ SIGNATURES = {
     'dw_edge_logreg_workspace_bytes': (ctypes.c_int, [_i64, _i32, _szp]),
     'dw_edge_logreg': (ctypes.c_int, [_p, _i64, _i32, _i32, _p, _p, _i64, _p, _p, _p,
                                       ctypes.c_size_t, _p, _p]),
+    'dw_edge_scores': (ctypes.c_int, [_p, _i64, _i32, _i32, _p, _i64, _p, _p, _p, _p]),
+    'dw_roc_auc_workspace_bytes': (ctypes.c_int, [_i64, _szp]),
+    'dw_roc_auc': (ctypes.c_int, [_p, _p, _i64, _p, _p, _p, ctypes.c_size_t, _p]),
+    'dw_edge_holdout_workspace_bytes': (ctypes.c_int, [_i64, _i64, _szp]),
+    'dw_edge_holdout_count': (ctypes.c_int, [_p, _p, _i64, _i64, _u64, _p, _p, _p,
+                                             ctypes.c_size_t, _p]),
+    'dw_edge_holdout': (ctypes.c_int, [_p, _p, _p, _i64, _i64, _u64, _i64, _i64, _p, _p, _p, _p,
+                                       _p, _p, ctypes.c_size_t, _p]),
     'dw_node_softmax_workspace_bytes': (ctypes.c_int, [_i64, _i32, _i32, _szp]),
     'dw_node_softmax': (ctypes.c_int, [_p, _i64, _i32, _p, _p, _i64, _i32, _p, _p, _p, _p,
                                        ctypes.c_size_t, _p, _p]),
@@ -315,4 +324,6 @@ def check_status(status: torch.Tensor, what: str) -> None:
         raise ValueError(f'{what}: malformed edge-list line')
     if s & DW_S_NEG_WEIGHT:
         raise ValueError(f'{what}: negative weight on an edge (weights must be >= 0)')
+    if s & DW_S_NAN_SCORE:
+        raise ValueError(f'{what}: a score is NaN (it has no rank)')
     raise RuntimeError(f'{what}: device status {s:#x}')

@@ -239,11 +239,26 @@ class GraphDownstreamEdgeClassificationConfig:
     # 'sklearn': the reference's host path over a networkx graph; 'device': the CSR path of
     # shallow_encoders/graph/linkpred.py (any graph dataset, graph_rmat included)
     backend: str = 'sklearn'
+    # 'reference': the reference's in-sample protocol (every edge is walked, then classified);
+    # 'heldout': node2vec §4.4 — the dataset hides edges (holdout_ratio > 0), the table is trained
+    # on the rest, the hidden edges are ranked against non-edges (ROC AUC; backend=device only)
+    protocol: str = 'reference'
+    # 'classifier': the fitted logistic regression's score; 'dot': the rows' dot product, no fit
+    scorer: str = 'classifier'
 
     def __post_init__(self):
         if self.backend not in ('sklearn', 'device'):
             raise ValueError(f'downstream.edge_classification.backend must be "sklearn" or '
                              f'"device", got {self.backend!r}')
+        if self.protocol not in ('reference', 'heldout'):
+            raise ValueError(f'downstream.edge_classification.protocol must be "reference" or '
+                             f'"heldout", got {self.protocol!r}')
+        if self.scorer not in ('classifier', 'dot'):
+            raise ValueError(f'downstream.edge_classification.scorer must be "classifier" or '
+                             f'"dot", got {self.scorer!r}')
+        if self.protocol == 'heldout' and self.backend != 'device':
+            raise ValueError('downstream.edge_classification.protocol=heldout runs on the device '
+                             'only: set downstream.edge_classification.backend=device')
 
 
 @dataclass

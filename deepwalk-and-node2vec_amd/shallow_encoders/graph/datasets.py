@@ -41,6 +41,8 @@ class RandomWalkDataset:
         rng: str = 'python',
         seed: int = 0,
         device=None,
+        holdout_ratio: float = 0.0,
+        holdout_seed: int = 0,
     ):
         """
         Args:
@@ -51,7 +53,15 @@ class RandomWalkDataset:
             method_params: walker parameters (p, q)
             labels / features: optional node annotations
             rng / seed / device: walker sampling mode (see random_walk_generator)
+            holdout_ratio / holdout_seed: above 0, hide that share of the edges before anything
+                else sees the graph (graph/holdout.py: a pure function of graph, ratio and seed;
+                CSR-built datasets only). The walker, the vocabulary and the noise weights then
+                see the residual graph; ``full_csr``, ``heldout_edges`` and ``holdout_info`` keep
+                the rest for held-out link prediction.
         """
+        self._full_csr, self._heldout_edges, self._holdout_info = None, None, None
+        if holdout_ratio:
+            graph = self._hold_out(graph, holdout_ratio, holdout_seed)
         self._graph = graph
         if isinstance(graph, CSRGraph):
             base_nodes = list(graph.names[1:])
@@ -82,6 +92,42 @@ class RandomWalkDataset:
         self._walks_per_node = walks_per_node
         self._index = 0
         self._epoch = 0
+
+    def _hold_out(self, graph, ratio: float, seed: int) -> CSRGraph:
+        """The residual graph of ``graph`` (split on the device when the graph was built there)."""
+        from shallow_encoders.graph.holdout import split_edges
+        if not isinstance(graph, CSRGraph):
+            raise ValueError('holdout_ratio needs a dataset built straight to CSR (graph_rmat, '
+                             'graph_edge_list): a networkx-backed dataset cannot hide edges')
+        on_device = graph.col is None and 'col' in graph._dev
+        train, held, info = split_edges(graph, ratio, seed,
+                                        device=graph._dev_device if on_device else None)
+        if info['n_hold'] == 0:
+            raise ValueError(f'holdout_ratio={ratio} hides no edge: {info["n_want"]} wanted, '
+                             f'{info["n_candidates"]} of {info["n_edges"]} edges can go without '
+                             f'isolating a node')
+        if info['n_hold'] < info['n_want']:
+            logger.warning(f'holdout_ratio={ratio} asks for {info["n_want"]} held-out edges; only '
+                           f'{info["n_hold"]} can go without isolating a node.')
+        self._full_csr, self._heldout_edges, self._holdout_info = graph, held, info
+        return train
+
+    # ---- held-out link prediction ------------------------------------------------------
+    @property
+    def full_csr(self) -> CSRGraph:
+        """The graph before any edge was held out (``csr`` itself without a holdout)."""
+        return self._full_csr if self._full_csr is not None else self.csr
+
+    @property
+    def heldout_edges(self):
+        """int64 [n_hold, 2] hidden edges (u, v), u < v, in vocabulary ids — a device tensor when
+        the graph was built on the device, else numpy; None without a holdout."""
+        return self._heldout_edges
+
+    @property
+    def holdout_info(self) -> Optional[dict]:
+        """{'n_edges', 'n_want', 'n_candidates', 'n_hold'} of the split; None without one."""
+        return self._holdout_info
 
     # ---- reference surface -------------------------------------------------------------
     @property
@@ -195,7 +241,7 @@ class GraphTriplets(RandomWalkDataset):
     NUM_CLUSTERS = 3
 
     def __init__(self, walks_per_node: int, walk_length: int, method: str = 'deepwalk', *,
-                 rng: str = 'python', seed: int = 0, device=None):
+                 rng: str = 'python', seed: int = 0, device=None, **holdout):
         import networkx as nx
         graph = nx.Graph()
         labels = {}
@@ -206,7 +252,8 @@ class GraphTriplets(RandomWalkDataset):
             for suffix in ['1', '2', '3']:
                 labels[f'{prefix}{suffix}'] = str(i)
         super().__init__(graph=graph, walks_per_node=walks_per_node, walk_length=walk_length,
-                         method=method, labels=labels, rng=rng, seed=seed, device=device)
+                         method=method, labels=labels, rng=rng, seed=seed, device=device,
+                         **holdout)
 
 
 @register_dataset('graph_karate_club')

@@ -15,6 +15,16 @@ stored:
     dw_edge_logreg pass over the pairs (loss, gradient and accuracy sums in float64);
   * ``edge_classification_device``: the experiment loop.
 
+Held-out link prediction (node2vec §4.4) reuses the sampler and the fit on a
+graph whose test edges were hidden before training (graph/holdout.py):
+
+  * ``edge_scores`` / ``EdgeLogisticRegression.decision_function``: dw_edge_scores — the score
+    z of every pair, the same gather as the fit's pass;
+  * ``roc_auc`` / ``roc_auc_counts``: dw_roc_auc — the tie-aware Mann-Whitney count as exact
+    integers, divided once on the host;
+  * ``heldout_edge_classification``: fit on the train graph's edges, rank the held edges against
+    fresh non-edges of the full graph.
+
 The graph is a ``CSRGraph`` in vocabulary ids (row 0 = ``<unk>``, nodes 1 .. V - 1).
 """
 import ctypes
@@ -173,6 +183,74 @@ def logreg_workspace(n: int, d: int, device) -> torch.Tensor:
     return torch.empty(max(int(nb.value) // 8, 1), dtype=torch.float64, device=device)
 
 
+# ------------------------------------------------------------------------------ scores and AUC
+def edge_scores(table: torch.Tensor, pairs: torch.Tensor, operator_name: str,
+                coef: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """float64 [n] device tensor z = w . operator(table[n1], table[n2]) + b0 (dw_edge_scores).
+    ``coef``: float64 [d + 1] (weights, then the intercept) on the device or as numpy; None means
+    unit weights and a zero intercept — with 'hadamard' the plain dot product of the rows."""
+    op = operator_id(operator_name)
+    table, pairs = _table_and_pairs(table, pairs)
+    dev = table.device
+    n, d = pairs.shape[0], table.shape[1]
+    if coef is not None:
+        coef = torch.as_tensor(coef, dtype=torch.float64).to(dev).contiguous()
+        if coef.shape != (d + 1,):
+            raise ValueError('coef must hold d + 1 float64 values (weights, then the intercept)')
+    z = torch.empty(n, dtype=torch.float64, device=dev)
+    if n == 0:
+        return z
+    st = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _native.call('dw_edge_scores', _native.ptr(table), table.shape[0], d, op,
+                     _native.ptr(pairs), n, _native.ptr(coef), _native.ptr(z), _native.ptr(st),
+                     _native.stream(dev))
+    _native.check_status(st, 'edge_scores')
+    return z
+
+
+def _check_auc_inputs(scores, labels) -> None:
+    if getattr(scores, 'ndim', None) != 1 or getattr(labels, 'shape', None) != scores.shape:
+        raise ValueError('scores and labels must be 1-d and of the same length')
+
+
+def auc_from_counts(u2: int, n_pos: int, n_neg: int) -> float:
+    """U2 / (2 n_pos n_neg); an empty class has no AUC (ValueError, as sklearn)."""
+    if n_pos == 0 or n_neg == 0:
+        raise ValueError('ROC AUC needs at least one positive and one negative sample')
+    return u2 / (2 * n_pos * n_neg)
+
+
+def roc_auc_counts(scores: torch.Tensor, labels: torch.Tensor) -> Tuple[int, int, int]:
+    """(U2, n_pos, n_neg) of float64 device scores and uint8 labels (dw_roc_auc): U2 = sum over
+    positives of 2 #{lower negatives} + #{tied negatives}, exact integers."""
+    _check_auc_inputs(scores, labels)
+    if scores.dtype != torch.float64 or labels.dtype != torch.uint8 or \
+            labels.device != scores.device:
+        raise ValueError('scores must be float64 and labels uint8, on one device')
+    dev = scores.device
+    n = scores.shape[0]
+    if n >= 1 << 31:
+        raise ValueError('roc_auc takes fewer than 2^31 scores')
+    out = torch.zeros(3, dtype=torch.int64, device=dev)
+    st = torch.zeros(1, dtype=torch.int32, device=dev)
+    nb = ctypes.c_size_t(0)
+    with torch.cuda.device(dev):
+        _native.call('dw_roc_auc_workspace_bytes', n, ctypes.byref(nb))
+        ws = torch.empty(max(int(nb.value), 1), dtype=torch.uint8, device=dev)
+        _native.call('dw_roc_auc', _native.ptr(scores.contiguous()),
+                     _native.ptr(labels.contiguous()), n, _native.ptr(out), _native.ptr(st),
+                     _native.ptr(ws), ws.numel(), _native.stream(dev))
+    _native.check_status(st, 'roc_auc')
+    u2, n_pos, n_neg = (int(v) for v in out.tolist())
+    return u2, n_pos, n_neg
+
+
+def roc_auc(scores: torch.Tensor, labels: torch.Tensor) -> float:
+    """Exact ROC AUC (ties count a half), sklearn's roc_auc_score up to one division."""
+    return auc_from_counts(*roc_auc_counts(scores, labels))
+
+
 # ------------------------------------------------------------------------------ the optimiser
 Closure = Callable[[np.ndarray], Tuple[float, np.ndarray]]
 
@@ -280,11 +358,15 @@ class EdgeLogisticRegression:
         sums = self._device_closure(table, pairs, labels)(self.full_coef())
         return float(sums[-1]) / n
 
+    def decision_function(self, table: torch.Tensor, pairs: torch.Tensor) -> torch.Tensor:
+        """float64 [n] device tensor of z = w . x + b per pair (dw_edge_scores)."""
+        return edge_scores(table, pairs, self.operator_name, self.full_coef())
+
 
 # ------------------------------------------------------------------------------ the experiment
-def positive_edges(csr, device=None) -> torch.Tensor:
+def positive_edges(csr, device=None, loops: bool = True) -> torch.Tensor:
     """int64 [E, 2] device tensor: the CSR entries with col >= row (each undirected edge once,
-    self-loops included), in row order."""
+    self-loops included; col > row without ``loops``), in row order."""
     dev = _native.require_device(device)
     d = csr.device_tensors(dev)
     row_ptr, col = d['row_ptr'], d['col']
@@ -294,7 +376,7 @@ def positive_edges(csr, device=None) -> torch.Tensor:
     rows = torch.repeat_interleave(torch.arange(csr.vocab_size, dtype=torch.int64, device=dev),
                                    deg, output_size=csr.nnz)
     cols = col[:csr.nnz].to(torch.int64)
-    keep = cols >= rows
+    keep = cols >= rows if loops else cols > rows
     return torch.stack([rows[keep], cols[keep]], dim=1).contiguous()
 
 
@@ -345,3 +427,87 @@ def edge_classification_device(table: torch.Tensor, csr, train_ratio: float, n_e
     if return_accuracies:
         return mean, best, accs
     return mean, best
+
+
+# ------------------------------------------------------------------------------ held-out edges
+SCORERS = ('classifier', 'dot')
+
+
+def heldout_negative_offsets(i: int, n_train: int, n_test: int) -> Tuple[int, int]:
+    """Experiment i owns the samples [i * (n_train + n_test), (i + 1) * (n_train + n_test)) of
+    the negative stream: its training negatives first, then its test negatives."""
+    base = i * (n_train + n_test)
+    return base, base + n_train
+
+
+def heldout_pairs(full_csr, train_pos: torch.Tensor, held: torch.Tensor, i: int, seed: int,
+                  device=None):
+    """Experiment i's (train pairs, train labels, test pairs, test labels): the train graph's
+    edges and the held edges as positives, as many negatives each — non-edges of the FULL graph,
+    from disjoint offset ranges of one stream."""
+    dev = train_pos.device
+    n_train, n_test = train_pos.shape[0], held.shape[0]
+    off_train, off_test = heldout_negative_offsets(i, n_train, n_test)
+    neg_train = negative_edges(full_csr, n_train, seed, offset=off_train, device=device)
+    neg_test = negative_edges(full_csr, n_test, seed, offset=off_test, device=device)
+
+    def labels(n):
+        return torch.cat([torch.ones(n, dtype=torch.uint8, device=dev),
+                          torch.zeros(n, dtype=torch.uint8, device=dev)])
+    return (torch.cat([train_pos, neg_train]), labels(n_train),
+            torch.cat([held, neg_test]), labels(n_test))
+
+
+def heldout_edge_classification(table: torch.Tensor, full_csr, train_csr, held,
+                                n_experiments: int, operator_name: str,
+                                classifier_params: Optional[dict] = None,
+                                scorer: str = 'classifier', seed: int = 0, device=None,
+                                return_experiments: bool = False):
+    """Link prediction on held-out edges (node2vec §4.4): ``table`` was trained on ``train_csr``
+    (graph/holdout.py's residual graph of ``full_csr``), ``held`` int64 [n, 2] are the hidden
+    edges. Per experiment the classifier is fitted on the train graph's non-loop edges against
+    as many non-edges of the full graph and tested on the held edges against ``len(held)`` more;
+    experiments differ only in their negatives. ``scorer='dot'`` ranks by the rows' dot product
+    instead and fits nothing (its accuracy thresholds the dot product at 0).
+
+    Returns {'edge_auc', 'edge_auc_std', 'edge_accuracy', 'edge_best'}: mean and (population)
+    standard deviation of the exact ROC AUC of the test scores, mean and best test accuracy; with
+    ``return_experiments`` also the per-experiment (aucs, accuracies)."""
+    if scorer not in SCORERS:
+        raise ValueError(f'scorer must be one of {SCORERS}, got {scorer!r}')
+    EdgeLogisticRegression.from_params(operator_name, classifier_params)   # refuse early
+    if table.shape[0] != full_csr.vocab_size or train_csr.vocab_size != full_csr.vocab_size:
+        raise ValueError(f'table has {table.shape[0]} rows, the full graph '
+                         f'{full_csr.vocab_size}, the train graph {train_csr.vocab_size}')
+    dev, _ = _checked_tensors(full_csr, device if device is not None else
+                              (table.device if table.is_cuda else None))
+    table = table.to(device=dev, dtype=torch.float32).contiguous()
+    held = torch.as_tensor(held, dtype=torch.int64).to(dev).reshape(-1, 2).contiguous()
+    train_pos = positive_edges(train_csr, dev, loops=False)
+    if held.shape[0] == 0 or train_pos.shape[0] == 0:
+        raise ValueError('held-out link prediction needs held edges and training edges')
+    aucs: List[float] = []
+    accs: List[float] = []
+    for i in range(n_experiments):
+        x_train, y_train, x_test, y_test = heldout_pairs(full_csr, train_pos, held, i, seed, dev)
+        if scorer == 'dot':
+            z = edge_scores(table, x_test, 'hadamard', None)
+            acc = float(((z > 0) == (y_test != 0)).double().mean())
+        else:
+            clf = EdgeLogisticRegression.from_params(operator_name, classifier_params)
+            clf.fit(table, x_train, y_train)
+            z = clf.decision_function(table, x_test)
+            acc = clf.score(table, x_test, y_test)
+        auc = roc_auc(z, y_test)
+        logger.info(f'Experiment {i}: held-out AUC {auc:.4f}, accuracy {100 * acc:.2f}%.')
+        aucs.append(auc)
+        accs.append(acc)
+    assert aucs, 'No experiments performed!'
+    result = {'edge_auc': float(np.mean(aucs)), 'edge_auc_std': float(np.std(aucs)),
+              'edge_accuracy': float(np.mean(accs)), 'edge_best': float(max(accs))}
+    logger.info(f'Held-out link prediction ({scorer}): AUC {result["edge_auc"]:.4f} +- '
+                f'{result["edge_auc_std"]:.4f}, accuracy {100 * result["edge_accuracy"]:.2f}% '
+                f'over {n_experiments} experiments.')
+    if return_experiments:
+        return result, aucs, accs
+    return result

@@ -23,6 +23,10 @@ non-neighbours (itself included). sklearn's LogisticRegression with the config's
 features, no 2-D plot; macro-F1 is logged beside the accuracy). A multi-label dataset
 (``graph_edge_list`` with ``multilabel=true``) runs on the device backend only: one-vs-rest
 logistic regression, micro- and macro-F1 under ``downstream.node_classification.prediction``.
+``downstream.edge_classification.protocol=heldout`` (device backend, a dataset with
+``holdout_ratio`` > 0) replaces the in-sample edge task by node2vec §4.4's: the edges the dataset
+hid before training are ranked against non-edges, reported as ``edge_auc`` (exact ROC AUC),
+``edge_auc_std``, ``edge_accuracy`` and ``edge_best``.
 Only the labelled vertices are classified: a ``graph_edge_list`` dataset's label file may cover
 a part of the nodes.
 """
@@ -242,6 +246,25 @@ def edge_classification_on_device(embeddings: np.ndarray, graph, ec) -> Tuple[fl
         classifier_params=ec.classifier_params, device=dev)
 
 
+def heldout_edge_classification_on_device(embeddings: np.ndarray, dataset, ec) -> Dict[str, float]:
+    """``protocol: heldout``: the dataset hid edges before training (``holdout_ratio`` > 0, the
+    same split here as in tools/train.py: it is a function of graph, ratio and seed); they are
+    ranked against non-edges of the full graph (linkpred.heldout_edge_classification)."""
+    import torch
+    from shallow_encoders import _native
+    from shallow_encoders.graph import linkpred
+    inner = getattr(dataset, 'dataset', dataset)
+    if getattr(inner, 'heldout_edges', None) is None:
+        raise ValueError('downstream.edge_classification.protocol=heldout needs a dataset that '
+                         'held edges out: set datamodule.additional_parameters.holdout_ratio=<r> '
+                         '(0 < r < 1; graph_rmat or graph_edge_list), for training as well')
+    dev = _native.require_device(None)
+    table = torch.from_numpy(np.ascontiguousarray(embeddings, dtype=np.float32)).to(dev)
+    return linkpred.heldout_edge_classification(
+        table, inner.full_csr, inner.csr, inner.heldout_edges, ec.n_experiments,
+        ec.operator_name, classifier_params=ec.classifier_params, scorer=ec.scorer, device=dev)
+
+
 def load_input_embeddings(cfg, dataset, checkpoint_path: str) -> np.ndarray:
     """Input-embedding table of a tools/train.py checkpoint (weights-only load)."""
     import torch
@@ -290,7 +313,9 @@ def main(argv=None) -> Dict[str, float]:
             nc.n_experiments, features=dataset.features if dataset.has_features else None,
             classifier_params=nc.classifier_params, plot_path=plot)
     ec = cfg.downstream.edge_classification
-    if ec.enable and ec.backend == 'device':
+    if ec.enable and ec.protocol == 'heldout':
+        result.update(heldout_edge_classification_on_device(emb, dataset, ec))
+    elif ec.enable and ec.backend == 'device':
         result['edge_accuracy'], result['edge_best'] = edge_classification_on_device(
             emb, dataset.graph, ec)
     elif ec.enable:

@@ -52,6 +52,7 @@ extern "C" {
 #define DW_S_FIXED_RANGE   128   /* a gradient term past the deterministic fixed-point range         */
 #define DW_S_BAD_TEXT      256   /* a line of an edge-list text is malformed (dw_edgelist_parse*)    */
 #define DW_S_NEG_WEIGHT    512   /* a negative edge weight reached dw_alias_build (no table law)     */
+#define DW_S_NAN_SCORE    1024   /* a NaN score reached dw_roc_auc (it has no rank)                  */
 
 #define DW_METHOD_DEEPWALK   0   /* random_walk_generator.py:56-72 ('deepwalk' and 'dfs')          */
 #define DW_METHOD_NODE2VEC   1   /* random_walk_generator.py:75-119                                  */
@@ -825,6 +826,61 @@ int dw_edge_logreg(const float *table, int64_t vocab_size, int32_t dim, int32_t 
                    const int64_t *pairs, const uint8_t *labels, int64_t n, const double *coef,
                    double *out, void *workspace, size_t workspace_bytes, int32_t *status,
                    void *stream);
+
+/* z_out double[n]: the score of every pair, z = w . x + b0 with x = op(a, b) in fp32 exactly as
+ * dw_edge_features computes it and everything after it in float64, as dw_edge_logreg (the same
+ * gather: a group of lanes owns a pair, several pairs in flight per group; no atomic and no
+ * reduction across pairs, so reruns are bit-identical). coef double[dim + 1] in DEVICE memory, or
+ * NULL for unit weights and a zero intercept: with op 1 (hadamard) that is the plain dot product
+ * of the two rows. 1 <= dim <= 512; 16-B loads when dim % 4 == 0 and table is 16-B aligned. An
+ * id outside [0, vocab_size) sets DW_S_BAD_INDEX and its pair scores as x = 0. */
+int dw_edge_scores(const float *table, int64_t vocab_size, int32_t dim, int32_t op,
+                   const int64_t *pairs, int64_t n, const double *coef, double *z_out,
+                   int32_t *status, void *stream);
+
+/* Exact ROC-AUC counts of n scores (double) with labels uint8[n] (non-zero = positive).
+ * out int64[3] (DEVICE memory): [0] = U2 = sum over positives i of 2 #{negatives j: s_j < s_i} +
+ * #{negatives j: s_j = s_i}, [1] = n_pos, [2] = n_neg; AUC = U2 / (2 n_pos n_neg), divided by the
+ * host (the tie-aware Mann-Whitney statistic, sklearn's roc_auc_score up to that division).
+ * Integer sums only: bit-identical on every run. -0.0 ties with +0.0, +-inf are ordinary values,
+ * a NaN sets DW_S_NAN_SCORE and leaves out unspecified. n < 2^31; n = 0 writes zeros. workspace:
+ * >= dw_roc_auc_workspace_bytes(n) bytes, 256-B aligned. */
+int dw_roc_auc_workspace_bytes(int64_t n, size_t *bytes);
+int dw_roc_auc(const double *scores, const uint8_t *labels, int64_t n, int64_t *out,
+               int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- held-out edge split (shallow_encoders/graph/holdout.py) ----------------
+ * Hides edges of a simple undirected CSR (distinct neighbours per row, both directed entries of
+ * every edge, a self-loop one entry, no neighbour on row 0) so that every node keeps one. With
+ * mix64 splitmix64's finaliser (z = x + 0x9E3779B97F4A7C15; z = (z ^ z >> 30) *
+ * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31), the priority of edge
+ * {u, v}, u < v, is mix64(((u << 32) | v) ^ mix64(seed)): distinct for distinct edges. Self-loops
+ * are never held and protect nothing. Every node protects its non-loop edge of smallest
+ * priority; the candidates are the non-loop edges neither endpoint protects; held are the n_hold
+ * candidates of smallest priority.
+ *
+ * dw_edge_holdout_count: counts int64[2] (DEVICE memory) = {E_nl, the non-loop edges;
+ * n_candidates}. The host reads them, fixes n_hold <= n_candidates and calls dw_edge_holdout
+ * with the SAME workspace, untouched in between (it holds the per-node minima and the
+ * candidates' priorities).
+ * dw_edge_holdout: row_ptr_out int64[n_rows + 1], col_out int32[nnz - 2 n_hold] and weights_out
+ * (when weights is not NULL) = the CSR without both entries of every held edge, each row
+ * compacted in order; held int64[n_hold, 2] = the held edges (u, v), u < v, in the order of
+ * their col > row entries in the input. n_hold = 0 copies the graph.
+ * A neighbour on row 0 or outside [1, n_rows) sets DW_S_BAD_CSR (the entry is kept, nothing out
+ * of range is read); counts that do not add up to nnz - 2 n_hold and n_hold set DW_S_DUP_NEIGHBOR
+ * (a repeated neighbour repeats a priority) and nothing is written out of range. n_rows and nnz
+ * below 2^31. workspace: >= dw_edge_holdout_workspace_bytes(n_rows, nnz) bytes, 256-B aligned.
+ * Integer atomics, a sort of distinct keys and a scan: reruns are bit-identical. */
+int dw_edge_holdout_workspace_bytes(int64_t n_rows, int64_t nnz, size_t *bytes);
+int dw_edge_holdout_count(const int64_t *row_ptr, const int32_t *col, int64_t n_rows, int64_t nnz,
+                          uint64_t seed, int64_t *counts, int32_t *status, void *workspace,
+                          size_t workspace_bytes, void *stream);
+int dw_edge_holdout(const int64_t *row_ptr, const int32_t *col, const double *weights,
+                    int64_t n_rows, int64_t nnz, uint64_t seed, int64_t n_candidates,
+                    int64_t n_hold, int64_t *row_ptr_out, int32_t *col_out, double *weights_out,
+                    int64_t *held, int32_t *status, void *workspace, size_t workspace_bytes,
+                    void *stream);
 
 /* One pass of a multinomial logistic regression over the rows table[ids[i]], no float64 copy of
  * the features stored — what sklearn's LogisticRegression.fit / .predict compute from
