@@ -274,10 +274,13 @@ class CSRGraph:
             d['weights'] = None if self.weights is None else torch.from_numpy(self.weights).to(dev)
             d['status'] = torch.zeros(1, dtype=torch.int32, device=dev)
             st = d['status']
+            # against col's own length: a row_ptr that ends elsewhere is malformed (and one that
+            # ends past it would send every later kernel out of the array)
+            n_col = d['col'].numel()
             with torch.cuda.device(dev):
                 _native.call('dw_csr_validate', _native.ptr(d['row_ptr']),
-                             _native.ptr(d['col']) if self.nnz else None, self.vocab_size,
-                             self.nnz, _native.ptr(st), _native.stream(dev))
+                             _native.ptr(d['col']) if n_col else None, self.vocab_size,
+                             n_col, _native.ptr(st), _native.stream(dev))
             _native.check_status(st, 'CSR validation')
         if need_sorted and 'col_sorted' not in d:
             d['col_sorted'] = self._sorted_copy(dev)

@@ -23,9 +23,10 @@ and the device walker run on this CSR see identical neighbour lists.
   * the host draws their patch targets from the numpy stream advanced past the edge draws;
   * dw_csr_from_edges builds the CSR.
 C5 (scale 24) then takes seconds instead of minutes and never materialises the edge list on
-the host. Both paths give identical arrays (tests/test_gpu_walks.py).
+the host. Both paths give identical arrays (tests/test_gpu_walks.py at scale; tests/
+test_gpu_graph_build.py at the small edge shapes, other seeds and other (a, b, c, d)).
 """
-from typing import Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
@@ -90,12 +91,13 @@ def name_width(n: int) -> int:
     return 7 if n <= 10_000_000 else 8
 
 
-def rmat_graph(scale: int, n_edges: int, seed: int = 0, device=None) -> CSRGraph:
+def rmat_graph(scale: int, n_edges: int, seed: int = 0, device=None,
+               abcd: Tuple[float, float, float, float] = RMAT_ABCD) -> CSRGraph:
     """The R-MAT graph as a CSR — built on the host (numpy), or in HBM when ``device`` is a
     HIP device (identical arrays)."""
     if device is not None and torch.device(device).type == 'cuda':
-        return rmat_graph_device(scale, n_edges, seed, device)
-    edges, _ = rmat_edges(scale, n_edges, seed)
+        return rmat_graph_device(scale, n_edges, seed, device, abcd)
+    edges, _ = rmat_edges(scale, n_edges, seed, abcd)
     return csr_from_edges(1 << scale, edges)
 
 
@@ -130,14 +132,16 @@ def _u64_pairs(values) -> np.ndarray:
                     dtype=np.uint64).reshape(-1)
 
 
-def rmat_graph_device(scale: int, n_edges: int, seed: int = 0, device='cuda') -> CSRGraph:
-    """rmat_graph built in HBM: same uniforms, same dedupe / patch / CSR order."""
+def _rmat_edges_device(scale: int, n_edges: int, seed: int, abcd, dev, room: int = 0,
+                       ws: Optional[torch.Tensor] = None):
+    """The draw and dedupe step alone (dw_rmat_edges): ``(edges, m, rng)`` — the device buffer
+    of packed ``u << 32 | v`` edges (int64[n_edges + room], the first ``m`` filled: the kept
+    draws in draw order), their count, and the numpy generator advanced past the
+    ``scale * n_edges`` draws. ``ws``: a workspace to use (None: one sized for this call)."""
     import ctypes
 
     from shallow_encoders import _native
-    dev = _native.require_device(device)
-    a, b, c, _ = RMAT_ABCD
-    n = 1 << scale
+    a, b, c, _ = abcd
     rng = np.random.default_rng(seed)
     st = rng.bit_generator.state['state']
     s0, inc = int(st['state']), int(st['inc'])
@@ -145,28 +149,48 @@ def rmat_graph_device(scale: int, n_edges: int, seed: int = 0, device='cuda') ->
     levels = _u64_pairs(_pcg_advance(s0, level * n_edges, table) for level in range(scale))
     jump = np.array([[x & 0xFFFFFFFFFFFFFFFF, x >> 64, y & 0xFFFFFFFFFFFFFFFF, y >> 64]
                      for x, y in table], dtype=np.uint64).reshape(-1)
+    with torch.cuda.device(dev):
+        if ws is None:
+            nbytes = ctypes.c_size_t(0)
+            _native.call('dw_ingest_workspace_bytes', scale, n_edges, 1, ctypes.byref(nbytes))
+            ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)
+        lv = torch.from_numpy(levels.view(np.int64)).to(dev)
+        jp = torch.from_numpy(jump.view(np.int64)).to(dev)
+        edges = torch.empty(n_edges + room, dtype=torch.int64, device=dev)
+        count = torch.zeros(1, dtype=torch.int64, device=dev)
+        _native.call('dw_rmat_edges', scale, n_edges, _native.ptr(lv), _native.ptr(jp),
+                     inc & 0xFFFFFFFFFFFFFFFF, inc >> 64, a, a + b, a + b + c,
+                     _native.ptr(edges), _native.ptr(count), _native.ptr(ws), ws.numel(),
+                     _native.stream(dev))
+        m = int(count[0])
+    rng.bit_generator.advance(scale * n_edges)
+    return edges, m, rng
+
+
+def rmat_graph_device(scale: int, n_edges: int, seed: int = 0, device='cuda',
+                      abcd: Tuple[float, float, float, float] = RMAT_ABCD) -> CSRGraph:
+    """rmat_graph built in HBM: same uniforms, same dedupe / patch / CSR order."""
+    import ctypes
+
+    from shallow_encoders import _native
+    dev = _native.require_device(device)
+    n = 1 << scale
     nbytes = ctypes.c_size_t(0)
     _native.call('dw_ingest_workspace_bytes', scale, n_edges + n, n, ctypes.byref(nbytes))
     with torch.cuda.device(dev):
         s = _native.stream(dev)
         ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)
-        lv = torch.from_numpy(levels.view(np.int64)).to(dev)
-        jp = torch.from_numpy(jump.view(np.int64)).to(dev)
-        edges = torch.empty(n_edges + n, dtype=torch.int64, device=dev)   # + room for patches
-        count = torch.zeros(2, dtype=torch.int64, device=dev)
+        # (room for the patch edges; the generator stands past the scale * n_edges edge draws)
+        edges, m, rng = _rmat_edges_device(scale, n_edges, seed, abcd, dev, room=n, ws=ws)
+        count = torch.zeros(1, dtype=torch.int64, device=dev)
         status = torch.zeros(1, dtype=torch.int32, device=dev)
-        _native.call('dw_rmat_edges', scale, n_edges, _native.ptr(lv), _native.ptr(jp),
-                     inc & 0xFFFFFFFFFFFFFFFF, inc >> 64, a, a + b, a + b + c,
-                     _native.ptr(edges), _native.ptr(count), _native.ptr(ws), ws.numel(), s)
-        m = int(count[0])
         iso_dev = torch.empty(n, dtype=torch.int32, device=dev)
         _native.call('dw_graph_isolated', _native.ptr(edges), m, n, _native.ptr(iso_dev),
-                     _native.ptr(count[1:]), _native.ptr(status), _native.ptr(ws), ws.numel(), s)
-        n_iso = int(count[1])
+                     _native.ptr(count), _native.ptr(status), _native.ptr(ws), ws.numel(), s)
+        n_iso = int(count[0])
         if n_iso:
-            # the patch targets come from the same numpy stream, past the scale*n_edges draws
+            # the patch targets come from the same numpy stream, past the edge draws
             iso = iso_dev[:n_iso].cpu().numpy().astype(np.int64)
-            rng.bit_generator.advance(scale * n_edges)
             tgt = rng.integers(0, n - 1, size=n_iso)
             tgt = tgt + (tgt >= iso)
             plo, phi = np.minimum(iso, tgt), np.maximum(iso, tgt)

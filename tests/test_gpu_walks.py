@@ -562,19 +562,27 @@ def test_node2vec_replay_refuses_repeated_neighbours(hip_device):
     Node2Vec(ok, 4, device=hip_device).walk_batch(torch.tensor([1], dtype=torch.int32))
 
 
-@pytest.mark.parametrize('which', ['karate', 'rmat12', 'self_loops'])
-def test_edge_common_counts_vs_host(which, hip_device):
+@pytest.mark.parametrize('which', ['karate', 'rmat12', 'self_loops', 'ladder_hubs'])
+def test_edge_common_counts_vs_host(which, hip_device, monkeypatch):
     """dw_edge_common_counts (the node2vec replay's per-edge class counts: one intersection per
     undirected edge over the shorter list, hub bitmaps or hashes) equals the oracle's
     restatement of the reference rule (walk_ref.edge_class_counts) on every directed edge,
-    including self-loops and hub-to-hub edges."""
+    including self-loops and hub-to-hub edges. 'ladder_hubs': the ladder graph of
+    tests/graph_ref.py with the bitmap threshold lowered to degree 16 (the kernels find a hub
+    through hub_idx alone), so the bitmap, hash and short-list branches all run on 3,000 entries."""
     if which == 'karate':
         csr = _csr(golden('walks_karate_node2vec_p1_q0.5.npz'))
     elif which == 'rmat12':
         csr = _csr(golden('walks_rmat12_node2vec_p0.25_q4.npz'))
+    elif which == 'ladder_hubs':
+        import graph_ref
+        monkeypatch.setenv('DW_HUB_MIN_DEGREE', '16')
+        csr = CSRGraph.from_arrays(*graph_ref.ladder_graph())
     else:
         csr = _self_loop_graph()
     d = csr.device_tensors(hip_device, need_edge_cn=True)
+    if which == 'ladder_hubs':
+        assert (d['hub_idx'] >= 0).sum() > 1
     got = d['edge_cn'][:csr.nnz].cpu().numpy().view(np.uint32)
     ref = walk_ref.edge_class_counts(walk_ref.CSR(csr.row_ptr, csr.host_col(), None))
     np.testing.assert_array_equal(got, ref)
