@@ -14,8 +14,10 @@
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include "dw_common.h"
+#include "dw_f32text.h"
 #include "dw_strtod.h"
 
 namespace {
@@ -272,6 +274,110 @@ int dw_noise_alias_build(const double *weights, int64_t V, uint64_t *table) {
     }
     free(scaled);
     free(stack);
+    return DW_OK;
+}
+
+
+// The table dw_f32text.h reads, with exact integers: 5^47 < 2^110 fits an unsigned __int128, and
+// the inverses come from a bit-by-bit long division whose remainder stays below 5^30 < 2^70.
+int dw_f32text_table(uint64_t *out) {
+    namespace ft = dw::f32text;
+    DW_REQUIRE(out, "dw_f32text_table: null pointer");
+    unsigned __int128 p = 1;
+    for (int i = 0; i < ft::POW_ENTRIES; ++i, p *= 5) {
+        const int b = static_cast<int>(ft::pow5bits(static_cast<uint32_t>(i)));
+        if (i < ft::INV_ENTRIES) {   // floor(2^(b - 1 + 59) / 5^i) + 1
+            unsigned __int128 r = 1;
+            uint64_t q = 0;
+            for (int j = 0; j < b - 1 + ft::INV_BITS; ++j) {
+                r <<= 1;
+                const bool one = r >= p;
+                if (one) r -= p;
+                q = (q << 1) | (one ? 1u : 0u);
+            }
+            out[i] = q + 1;
+        }
+        out[ft::INV_ENTRIES + i] = static_cast<uint64_t>(
+            b >= ft::POW_BITS ? p >> (b - ft::POW_BITS) : p << (ft::POW_BITS - b));
+    }
+    return DW_OK;
+}
+
+// The host mirror of dw_embtext_sizes (out == NULL) and dw_embtext_write (out != NULL): the same
+// per-value code (dw_f32text.h), one row after the other.
+int dw_embtext_host(const float *table, int64_t vocab_size, int32_t dim, const int64_t *rows,
+                    int64_t n_rows, const int64_t *keys_i64, const uint8_t *key_bytes,
+                    const int64_t *key_off, int64_t *line_off, int64_t r0, int64_t r1,
+                    uint8_t *out, int64_t capacity, int32_t *status) {
+    namespace ft = dw::f32text;
+    DW_REQUIRE(table && line_off && status, "dw_embtext_host: null pointer");
+    DW_REQUIRE(vocab_size >= 1 && n_rows >= 0, "dw_embtext_host: bad sizes");
+    DW_REQUIRE(dim >= 1, "dw_embtext_host: dim must be >= 1");
+    DW_REQUIRE((keys_i64 != nullptr) != (key_bytes != nullptr && key_off != nullptr),
+               "dw_embtext_host: give keys_i64 or (key_bytes, key_off), not both");
+    static uint64_t tab[ft::TABLE_WORDS];
+    static const int tab_ok = dw_f32text_table(tab);
+    (void)tab_ok;
+    if (out) {
+        DW_REQUIRE(0 <= r0 && r0 <= r1 && r1 <= n_rows, "dw_embtext_host: bad row range");
+        DW_REQUIRE(capacity >= 0 && line_off[r1] - line_off[r0] <= capacity,
+                   "dw_embtext_host: rows [%lld, %lld) need %lld bytes, the buffer holds %lld",
+                   (long long)r0, (long long)r1, (long long)(line_off[r1] - line_off[r0]),
+                   (long long)capacity);
+    } else {
+        r0 = 0;
+        r1 = n_rows;
+        line_off[0] = 0;
+    }
+    int32_t st = 0;
+    for (int64_t r = r0; r < r1; ++r) {
+        int64_t src = rows ? rows[r] : r;
+        const bool bad_row = src < 0 || src >= vocab_size;
+        if (bad_row) st |= DW_S_BAD_INDEX;
+        int64_t key = 0, klen;
+        if (keys_i64) {
+            key = keys_i64[r];
+            if (key < 0) {
+                st |= DW_S_BAD_INDEX;
+                key = 0;
+            }
+            klen = ft::key_digits(key);
+        } else {
+            klen = key_off[r + 1] - key_off[r];
+            if (klen < 0) {
+                st |= DW_S_BAD_INDEX;
+                klen = 0;
+            }
+        }
+        uint8_t *w = out ? out + (line_off[r] - line_off[r0]) : nullptr;
+        if (w) {
+            if (keys_i64) {
+                uint64_t v = static_cast<uint64_t>(key);
+                for (int64_t j = klen - 1; j >= 0; --j, v /= 10u)
+                    w[j] = static_cast<uint8_t>('0' + v % 10u);
+            } else {
+                for (int64_t j = 0; j < klen; ++j) w[j] = key_bytes[key_off[r] + j];
+            }
+            w += klen;
+        }
+        int64_t len = klen + 1;
+        for (int32_t c = 0; c < dim; ++c) {
+            uint32_t bits = 0;
+            if (!bad_row) memcpy(&bits, table + src * dim + c, 4);
+            const ft::Dec d = ft::shortest(bits, tab);
+            if (d.kind != ft::FINITE) st |= DW_S_NONFINITE;
+            len += 1 + ft::token_len(d);
+            if (w) {
+                *w++ = ' ';
+                ft::token_emit(d, [&w](uint8_t b) { *w++ = b; });
+            }
+        }
+        if (w)
+            *w++ = '\n';
+        else
+            line_off[r + 1] = line_off[r] + len;
+    }
+    *status |= st;
     return DW_OK;
 }
 

@@ -35,6 +35,7 @@ DW_S_FIXED_RANGE = 128
 DW_S_BAD_TEXT = 256
 DW_S_NEG_WEIGHT = 512
 DW_S_NAN_SCORE = 1024
+DW_S_NONFINITE = 2048
 DW_EXACT_DEFER = 1
 DW_EXACT_ADAM = 2
 
@@ -44,7 +45,7 @@ DW_METHOD_NODE2VEC = 1
 DW_OVR_THRESHOLD = 0
 DW_OVR_TOP_K = 1
 
-ABI_VERSION = 34
+ABI_VERSION = 35
 
 _p = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -86,6 +87,14 @@ SIGNATURES = {
                                                   _p, _p, _p, _p, ctypes.c_size_t, _p]),
     'dw_pow5_table': (ctypes.c_int, [_p]),
     'dw_weight_token_host': (ctypes.c_int, [_p, _i64, _p, _p]),
+    'dw_f32text_table': (ctypes.c_int, [_p]),
+    'dw_embtext_host': (ctypes.c_int, [_p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _i64, _i64, _p,
+                                       _i64, _p]),
+    'dw_embtext_workspace_bytes': (ctypes.c_int, [_i64, _i32, _szp]),
+    'dw_embtext_sizes': (ctypes.c_int, [_p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _p, _p,
+                                        ctypes.c_size_t, _p]),
+    'dw_embtext_write': (ctypes.c_int, [_p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _i64, _i64,
+                                        _p, _i64, _p, _p]),
     'dw_edges_canonical': (ctypes.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _p, _p, _p, _p,
                                           ctypes.c_size_t, _p]),
     'dw_csr_from_edges_loops': (ctypes.c_int, [_p, _p, _i64, _i64, _p, _p, _p, _p, _p,
@@ -326,4 +335,6 @@ def check_status(status: torch.Tensor, what: str) -> None:
         raise ValueError(f'{what}: negative weight on an edge (weights must be >= 0)')
     if s & DW_S_NAN_SCORE:
         raise ValueError(f'{what}: a score is NaN (it has no rank)')
+    if s & DW_S_NONFINITE:
+        raise ValueError(f'{what}: a value is nan or inf')
     raise RuntimeError(f'{what}: device status {s:#x}')

@@ -21,6 +21,8 @@ MI355X additions (all optional, defaulted, so reference configs load as they are
                           drawn once per walk (noise 'device' or 'unigram'), the step one MFMA
                           kernel (dw_sgns_walks_shared) and the optimizer's dense Adam; a departure
                           from the reference's negatives per pair
+  export.*                tools/export_embeddings.py: the table, path, key style and device of
+                          the word2vec-text export (ExportConfig)
 ``_target_: torch.optim.Adam`` instantiates the HIP Adam and ``_target_: torch.optim.SGD`` the HIP
 SGD (word2vec/optim.py, same math).
 """
@@ -271,6 +273,26 @@ class GraphDownstreamTaskConfig:
 
 
 @dataclass
+class ExportConfig:
+    """tools/export_embeddings.py: a checkpoint's table (analysis.checkpoint) as word2vec text."""
+    table: str = 'input'          # 'input' | 'output': the input table is what downstream reads
+    path: Optional[str] = None    # default: embeddings.emb in the experiment's analysis directory
+    keys: str = 'id'              # 'id': the user's node names or ids | 'token': vocabulary tokens
+    include_unk: bool = False
+    nonfinite: str = 'error'      # 'error' | 'write'
+    device: str = 'auto'          # 'auto': the GPU when one is visible | 'cpu' | 'cuda[:i]'
+
+    def __post_init__(self):
+        if self.table not in ('input', 'output'):
+            raise ValueError(f'export.table must be "input" or "output", got {self.table!r}')
+        if self.keys not in ('id', 'token'):
+            raise ValueError(f'export.keys must be "id" or "token", got {self.keys!r}')
+        if self.nonfinite not in ('error', 'write'):
+            raise ValueError(f'export.nonfinite must be "error" or "write", got '
+                             f'{self.nonfinite!r}')
+
+
+@dataclass
 class PathConfig:
     output_dir: str = RUNS_PATH
 
@@ -283,6 +305,7 @@ class GlobalConfig:
     analysis: ModelAnalysisConfig = field(default_factory=ModelAnalysisConfig)
     path: PathConfig = field(default_factory=PathConfig)
     downstream: GraphDownstreamTaskConfig = field(default_factory=GraphDownstreamTaskConfig)
+    export: ExportConfig = field(default_factory=ExportConfig)
 
     def instantiate_model(self, dataset=None):
         dataset = self.datamodule.instantiate_dataset() if dataset is None else dataset

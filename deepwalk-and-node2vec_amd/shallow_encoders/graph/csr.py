@@ -249,6 +249,29 @@ class CSRGraph:
             self.__dict__['_stoi_cache'] = sto
         return sto[tok]
 
+    def export_keys(self, style: str = 'id', include_unk: bool = False):
+        """The first column of an exported embedding file (word2vec/embeddings_io.py), one key
+        per vocabulary row from row 1 on (from row 0, ``<unk>``, with include_unk).
+
+        style 'id': the names the user's own data uses — an edge-list graph's ids (int64, so
+        the column matches the edge file), a synthetic graph's node numbers i - 1 (int64), else
+        ``str(name)`` of the node objects. style 'token': the vocabulary tokens (``n0000003``).
+        With include_unk the integer forms become strings behind ``<unk>``."""
+        if style not in ('id', 'token'):
+            raise ValueError(f'export_keys: style must be "id" or "token", got {style!r}')
+        V = self.vocab_size
+        if style == 'token':
+            return list(self.itos[0 if include_unk else 1:V])
+        if isinstance(self.itos, IdNames):
+            ids = self.itos.ids
+        elif isinstance(self.itos, NodeNames):
+            ids = np.arange(V - 1, dtype=np.int64)
+        else:
+            names = [self.itos[i] if self.names[i] is None else str(self.names[i])
+                     for i in range(1, V)]
+            return ([UNK] if include_unk else []) + names
+        return [UNK] + [str(int(i)) for i in ids] if include_unk else ids
+
     # ------------------------------------------------------------------ device side
     def device_tensors(self, device=None, need_sorted: bool = False,
                        need_alias: bool = False, need_edges: bool = False,

@@ -53,6 +53,7 @@ extern "C" {
 #define DW_S_BAD_TEXT      256   /* a line of an edge-list text is malformed (dw_edgelist_parse*)    */
 #define DW_S_NEG_WEIGHT    512   /* a negative edge weight reached dw_alias_build (no table law)     */
 #define DW_S_NAN_SCORE    1024   /* a NaN score reached dw_roc_auc (it has no rank)                  */
+#define DW_S_NONFINITE    2048   /* a nan or inf value reached the embedding text writer             */
 
 #define DW_METHOD_DEEPWALK   0   /* random_walk_generator.py:56-72 ('deepwalk' and 'dfs')          */
 #define DW_METHOD_NODE2VEC   1   /* random_walk_generator.py:75-119                                  */
@@ -256,6 +257,54 @@ int dw_pow5_table(uint64_t *out);
 #define DW_TOKEN_DECIDED   1
 #define DW_TOKEN_UNDECIDED 2
 int dw_weight_token_host(const uint8_t *token, int64_t n_bytes, int32_t *kind, uint64_t *bits);
+
+/* ---- Embeddings to word2vec text (shallow_encoders/word2vec/embeddings_io.py): line r is
+ * "<key r> <T(v_0)> .. <T(v_{dim-1})>\n" for row rows[r] of table (float32 [vocab_size, dim];
+ * rows int64 [n_rows], NULL = rows 0 .. n_rows - 1), single spaces, no '\r'. The key is
+ * keys_i64[r] in plain decimal (int64 [n_rows], >= 0) or the bytes key_bytes[key_off[r],
+ * key_off[r + 1]) (key_off int64 [n_rows + 1]); exactly one of the two forms is given. T(x) is the
+ * shortest decimal that rounds back to the float32 x, laid out as CPython's repr(float) lays out
+ * a double with those digits ("0.0", "-0.0", "0.0001", "1e-05", "9999999000000000.0", "1e+16";
+ * "nan", "inf", "-inf"); at most 19 bytes. It is computed in integer arithmetic alone (Ryu for
+ * binary32 over tab: uint64 [79], the words of dw_f32text_table). A row id outside
+ * [0, vocab_size) sets DW_S_BAD_INDEX and prints as zeros, a negative key sets it and prints as
+ * 0; a nan or inf value sets DW_S_NONFINITE (its token is still written). dim > 512 returns
+ * DW_E_UNSUPPORTED before any launch. Every output is a pure function of the input. */
+
+/* Host only: the 79 words the conversion reads — for q = 0 .. 30 floor(2^(b(q) - 1 + 59) / 5^q)
+ * + 1, then for i = 0 .. 47 the top 61 bits of 5^i (b = the bit length of the power), computed
+ * with exact integers. out: host uint64 [79]. */
+int dw_f32text_table(uint64_t *out);
+
+/* Host only (no device; every pointer is host memory): both passes below in one entry point, the
+ * CPU path of save_word2vec_format and the kernels' mirror for tests. out == NULL: writes line_off
+ * [n_rows + 1] and ORs the status bits of all rows into *status (r0, r1, capacity ignored).
+ * out != NULL: writes the lines of rows [r0, r1) at out + line_off[r] - line_off[r0];
+ * DW_E_INVALID_ARG, with nothing written, when they need more than capacity bytes. */
+int dw_embtext_host(const float *table, int64_t vocab_size, int32_t dim, const int64_t *rows,
+                    int64_t n_rows, const int64_t *keys_i64, const uint8_t *key_bytes,
+                    const int64_t *key_off, int64_t *line_off, int64_t r0, int64_t r1,
+                    uint8_t *out, int64_t capacity, int32_t *status);
+
+int dw_embtext_workspace_bytes(int64_t n_rows, int32_t dim, size_t *bytes);
+
+/* Pass 1: line_off (device int64 [n_rows + 1]) = the exclusive scan of the lines' byte lengths,
+ * the total in its last entry; the status bits above. */
+int dw_embtext_sizes(const float *table, int64_t vocab_size, int32_t dim, const int64_t *rows,
+                     int64_t n_rows, const int64_t *keys_i64, const uint8_t *key_bytes,
+                     const int64_t *key_off, const uint64_t *tab, int64_t *line_off,
+                     int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Pass 2: the lines of rows [r0, r1) into out (device uint8 [capacity]) at line_off[r] -
+ * line_off[r0], with the inputs and the line_off of pass 1. When line_off[r1] - line_off[r0]
+ * exceeds capacity nothing is written and DW_S_RECORDS_FULL is set (line_off lives on the
+ * device: the launch does not wait for it). No byte at or past line_off[r1] - line_off[r0] is
+ * stored, and no line stores outside its own [line_off[r], line_off[r + 1]). */
+int dw_embtext_write(const float *table, int64_t vocab_size, int32_t dim, const int64_t *rows,
+                     int64_t n_rows, const int64_t *keys_i64, const uint8_t *key_bytes,
+                     const int64_t *key_off, const uint64_t *tab, const int64_t *line_off,
+                     int64_t r0, int64_t r1, uint8_t *out, int64_t capacity, int32_t *status,
+                     void *stream);
 
 /* Raw edges (src, dst int64 [n_edges], ids in [0, 2^id_bits), id_bits <= 60: others set
  * DW_S_BAD_INDEX; weights float64 [n_edges] or NULL) to their canonical form: node_ids int64
