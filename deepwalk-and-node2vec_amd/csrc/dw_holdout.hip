@@ -10,6 +10,11 @@
 //   dw_edge_holdout_count   per-node minimum priority; the unprotected priorities, compacted;
 //                           E_nl and n_candidates for the host, which fixes n_hold
 //   dw_edge_holdout         sort the candidates (T = the n_hold-th), flag every entry, scan, write
+//   dw_edge_forest          the minimum spanning forest of the non-loop edges under prio (Boruvka,
+//                           below) and every row's connected component
+//   dw_edge_holdout_count_protected / dw_edge_holdout_protected
+//                           the same split with the protected entries given as flags (the forest:
+//                           the residual graph keeps the full graph's components)
 //
 // Every kernel is entry-parallel: thread e owns directed entry e and finds its row by a binary
 // search of row_ptr once (k_min_prio keeps it in `rows`), so a 44,848-neighbour hub and a
@@ -77,6 +82,35 @@ int plan(Arena &a, int64_t n_rows, int64_t nnz, Bufs *p) {
     return DW_OK;
 }
 
+// The row of entry e: the r in [0, n_rows - 1] with row_ptr[r] <= e < row_ptr[r + 1].
+__device__ __forceinline__ int32_t row_of(const int64_t *__restrict__ row_ptr, int64_t n_rows,
+                                          int64_t e) {
+    int64_t lo = 0, hi = n_rows - 1;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (row_ptr[mid + 1] > e)
+            hi = mid;
+        else
+            lo = mid + 1;
+    }
+    return static_cast<int32_t>(lo);
+}
+
+// Which non-loop entries the split never hides: entry e = x -> y of priority p. Both directed
+// entries of an edge get the same answer under either rule.
+struct ByMinimum {   // the edge of smallest priority at either endpoint
+    const uint64_t *__restrict__ minp;
+    __device__ __forceinline__ bool operator()(int64_t, int64_t x, int64_t y, uint64_t p) const {
+        return p == minp[x] || p == minp[y];
+    }
+};
+struct ByFlag {      // the caller's flags (dw_edge_forest's)
+    const uint8_t *__restrict__ flag;
+    __device__ __forceinline__ bool operator()(int64_t e, int64_t, int64_t, uint64_t) const {
+        return flag[e] != 0;
+    }
+};
+
 __global__ void __launch_bounds__(256) k_fill(uint64_t *__restrict__ dst, int64_t n, uint64_t v) {
     const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
     if (i < n) dst[i] = v;
@@ -93,17 +127,9 @@ __global__ void __launch_bounds__(256)
     int32_t row = INT32_MAX;   // past the end: above every row, so a wave's rows stay sorted
     uint64_t p = NO_PRIO;
     if (e < nnz) {
-        int64_t lo = 0, hi = n_rows - 1;   // the answer lies in [0, n_rows - 1]
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (row_ptr[mid + 1] > e)
-                hi = mid;
-            else
-                lo = mid + 1;
-        }
-        row = static_cast<int32_t>(lo);
+        row = row_of(row_ptr, n_rows, e);
         rows[e] = row;
-        const int64_t x = lo, y = col[e];
+        const int64_t x = row, y = col[e];
         if (!entry_ok(x, y, n_rows))
             dw::status_or(status, DW_S_BAD_CSR);
         else if (x != y)
@@ -133,9 +159,10 @@ __global__ void __launch_bounds__(256)
 constexpr int CAND_PER = 8;
 constexpr int CAND_TILE = 256 * CAND_PER;
 
+template <class Protect>
 __global__ void __launch_bounds__(256)
     k_candidates(const int32_t *__restrict__ col, const int32_t *__restrict__ rows,
-                 int64_t n_rows, int64_t nnz, uint64_t mseed, const uint64_t *__restrict__ minp,
+                 int64_t n_rows, int64_t nnz, uint64_t mseed, const Protect is_protected,
                  uint64_t *__restrict__ cand, unsigned long long *counts) {
     __shared__ uint32_t s_cand[4], s_edges[4];
     __shared__ unsigned long long s_base;
@@ -152,7 +179,7 @@ __global__ void __launch_bounds__(256)
             if (entry_ok(x, y, n_rows) && y > x) {
                 ++n_edges;
                 p[k] = edge_prio(x, y, mseed);
-                if (p[k] != minp[x] && p[k] != minp[y]) mask |= 1u << k;
+                if (!is_protected(e, x, y, p[k])) mask |= 1u << k;
             }
         }
     }
@@ -188,9 +215,10 @@ __global__ void __launch_bounds__(256)
 
 // flags[e]: bit 0 = the entry stays in the train CSR, bit 32 = it is the col > row entry of a
 // held edge (one sum scans both counts: each stays below 2^31). flags[nnz] = 0 closes the scan.
+template <class Protect>
 __global__ void __launch_bounds__(256)
     k_flags(const int32_t *__restrict__ col, const int32_t *__restrict__ rows, int64_t n_rows,
-            int64_t nnz, uint64_t mseed, const uint64_t *__restrict__ minp,
+            int64_t nnz, uint64_t mseed, const Protect is_protected,
             const uint64_t *__restrict__ threshold, uint64_t *__restrict__ flags) {
     const int64_t e = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
     if (e > nnz) return;
@@ -200,7 +228,7 @@ __global__ void __launch_bounds__(256)
         const int64_t x = rows[e], y = col[e];
         if (threshold && entry_ok(x, y, n_rows) && x != y) {
             const uint64_t p = edge_prio(x, y, mseed);
-            if (p != minp[x] && p != minp[y] && p <= *threshold)
+            if (!is_protected(e, x, y, p) && p <= *threshold)
                 f = y > x ? uint64_t(1) << 32 : 0;
         }
     }
@@ -256,9 +284,382 @@ int check_sizes(const char *who, int64_t n_rows, int64_t nnz) {
     return DW_OK;
 }
 
+// ---- minimum spanning forest and connected components (Boruvka on the CSR) -----------------------
+// Every vertex carries the label comp[v] of its tree's root; parent[c] == c marks a root. A round:
+//
+//   k_comp_min   best[c] = the smallest priority among the entries that leave component c
+//   k_hook       the entry that holds best[c] is a forest edge and hangs c under the other side's
+//                root; two components that pick the same edge keep the smaller label as the root.
+//                Distinct priorities allow no other cycle: along a chain of hooks best[] falls
+//                strictly (the far side sees the mate entry, so its best is <= this one's), and a
+//                far side whose best is larger (a CSR that lacks the mate entry) is refused
+//   k_compress   comp[v] = the root above comp[v]; best[] is cleared for the next round
+//
+// Components that still have a leaving edge at least halve per round, so ceil(log2 n_rows) rounds
+// always suffice and that many are launched, with no host read in between: ctrl[r + 1] says
+// whether round r hooked anything (ctrl[0] = 1), and a round's kernels return at once when the
+// round before hooked nothing. Integer atomics and same-value stores only: reruns are identical.
+struct ForestBufs {
+    int32_t *rows, *comp, *parent, *minid, *ctrl;
+    uint64_t *best;
+};
+
+int forest_rounds(int64_t n_rows) {   // ceil(log2(n_rows)), at least 1
+    int r = 0;
+    while ((int64_t(1) << r) < n_rows) ++r;
+    return r > 0 ? r : 1;
+}
+
+void forest_plan(Arena &a, int64_t n_rows, int64_t nnz, ForestBufs *p) {
+    const size_t n = static_cast<size_t>(nnz > 0 ? nnz : 1), v = static_cast<size_t>(n_rows);
+    p->rows = a.take<int32_t>(n);
+    p->comp = a.take<int32_t>(v);
+    p->parent = a.take<int32_t>(v);
+    p->minid = a.take<int32_t>(v);
+    p->ctrl = a.take<int32_t>(static_cast<size_t>(forest_rounds(n_rows)) + 1);
+    p->best = a.take<uint64_t>(v);
+}
+
+__global__ void __launch_bounds__(256)
+    k_forest_init(int64_t n_rows, int n_ctrl, int32_t *__restrict__ comp,
+                  int32_t *__restrict__ parent, int32_t *__restrict__ minid,
+                  uint64_t *__restrict__ best, int32_t *__restrict__ ctrl) {
+    const int64_t v = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (v < n_ctrl) ctrl[v] = v == 0;
+    if (v >= n_rows) return;
+    comp[v] = parent[v] = static_cast<int32_t>(v);
+    minid[v] = INT32_MAX;
+    best[v] = NO_PRIO;
+}
+
+__global__ void __launch_bounds__(256)
+    k_forest_rows(const int64_t *__restrict__ row_ptr, const int32_t *__restrict__ col,
+                  int64_t n_rows, int64_t nnz, int32_t *__restrict__ rows, int32_t *status) {
+    const int64_t e = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (e >= nnz) return;
+    const int32_t row = row_of(row_ptr, n_rows, e);
+    rows[e] = row;
+    if (!entry_ok(row, col[e], n_rows)) dw::status_or(status, DW_S_BAD_CSR);
+}
+
+// A value that only falls, so a stale read is safe: it can only let through an atomic that
+// changes nothing. Without the read, the late rounds send every boundary entry of the giant
+// component to one L2 word (k_candidates' note has what that costs).
+__device__ __forceinline__ void min_if_lower(uint64_t *word, uint64_t p) {
+    if (p < __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+        atomicMin(reinterpret_cast<unsigned long long *>(word), static_cast<unsigned long long>(p));
+}
+
+__global__ void __launch_bounds__(256)
+    k_comp_min(const int32_t *__restrict__ col, const int32_t *__restrict__ rows, int64_t n_rows,
+               int64_t nnz, uint64_t mseed, const int32_t *__restrict__ comp,
+               const int32_t *__restrict__ gate, uint64_t *best) {
+    if (*gate == 0) return;
+    const int64_t e = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    int32_t row = INT32_MAX;
+    uint64_t p = NO_PRIO;
+    if (e < nnz) {
+        row = rows[e];
+        const int64_t x = row, y = col[e];
+        if (entry_ok(x, y, n_rows) && x != y && comp[x] != comp[y]) p = edge_prio(x, y, mseed);
+    }
+    // k_min_prio's segmented minimum: a row's entries share comp[row]
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint64_t other = __shfl_down(static_cast<unsigned long long>(p), off, 64);
+        const int32_t other_row = __shfl_down(row, off, 64);
+        if (lane + off < 64 && other_row == row && other < p) p = other;
+    }
+    const int32_t before = __shfl_up(row, 1, 64);
+    if ((lane == 0 || before != row) && p != NO_PRIO) min_if_lower(best + comp[row], p);
+}
+
+__global__ void __launch_bounds__(256)
+    k_hook(const int32_t *__restrict__ col, const int32_t *__restrict__ rows, int64_t n_rows,
+           int64_t nnz, uint64_t mseed, const int32_t *__restrict__ comp,
+           const uint64_t *__restrict__ best, const int32_t *__restrict__ gate,
+           int32_t *__restrict__ parent, uint8_t *__restrict__ forest, int32_t *__restrict__ hooked,
+           int32_t *status) {
+    if (*gate == 0) return;
+    const int64_t e = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (e >= nnz) return;
+    const int64_t x = rows[e], y = col[e];
+    if (!entry_ok(x, y, n_rows) || x == y) return;
+    const int32_t cx = comp[x], cy = comp[y];
+    if (cx == cy) return;
+    const uint64_t p = edge_prio(x, y, mseed), bx = best[cx], by = best[cy];
+    if (p == bx || p == by) forest[e] = 1;
+    if (p != bx) return;
+    if (by > p) {   // y's side never saw this edge: the CSR lacks the entry y -> x
+        dw::status_or(status, DW_S_BAD_CSR);
+        return;
+    }
+    if (by == p && cx < cy) return;   // a mutual pick: the smaller label stays the root
+    parent[cx] = cy;
+    *hooked = 1;
+}
+
+__global__ void __launch_bounds__(256)
+    k_compress(int64_t n_rows, const int32_t *__restrict__ parent,
+               const int32_t *__restrict__ gate, int32_t *__restrict__ comp,
+               uint64_t *__restrict__ best) {
+    if (*gate == 0) return;
+    const int64_t v = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    if (v >= n_rows) return;
+    int32_t c = comp[v], q;
+    while ((q = parent[c]) != c) c = q;   // parent is not written here and holds no cycle
+    comp[v] = c;
+    best[v] = NO_PRIO;
+}
+
+// minid[c] = the smallest row of the tree rooted at c. Lanes hold ascending rows, so the first
+// lane of a run of equal roots has the run's smallest; it reads before it asks, as above.
+__global__ void __launch_bounds__(256)
+    k_comp_minid(int64_t n_rows, const int32_t *__restrict__ comp, int32_t *minid) {
+    const int64_t v = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const int32_t c = v < n_rows ? comp[v] : -1;
+    const int32_t before = __shfl_up(c, 1, 64);
+    if (c >= 0 && (lane == 0 || before != c) &&
+        static_cast<int32_t>(v) < __hip_atomic_load(minid + c, __ATOMIC_RELAXED,
+                                                    __HIP_MEMORY_SCOPE_AGENT))
+        atomicMin(minid + c, static_cast<int32_t>(v));
+}
+
+__device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t *s_part) {   // 256 threads
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return s_part[0] + s_part[1] + s_part[2] + s_part[3];
+}
+
+// component[v] = its tree's smallest row; counts[2] += the components that hold a non-loop edge
+// (their smallest row has one); counts[3] = the rounds that hooked; the last allowed round must
+// not have.
+__global__ void __launch_bounds__(256)
+    k_forest_labels(const int64_t *__restrict__ row_ptr, const int32_t *__restrict__ col,
+                    int64_t n_rows, int64_t nnz, const int32_t *__restrict__ comp,
+                    const int32_t *__restrict__ minid, const int32_t *__restrict__ ctrl,
+                    int max_rounds, int32_t *__restrict__ component, unsigned long long *counts,
+                    int32_t *status) {
+    __shared__ uint32_t s_part[4];
+    const int64_t v = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+    uint32_t heads = 0;
+    if (v < n_rows) {
+        const int32_t label = minid[comp[v]];
+        component[v] = label;
+        if (label == v && v >= 1) {
+            int64_t e = row_ptr[v], end = row_ptr[v + 1];
+            e = e < 0 ? 0 : e;
+            end = end > nnz ? nnz : end;
+            for (; e < end && !heads; ++e) heads = col[e] != v;
+        }
+    }
+    const uint32_t total = block_sum(heads, s_part);
+    if (threadIdx.x == 0 && total) atomicAdd(counts + 2, static_cast<unsigned long long>(total));
+    if (v == 0) {
+        int used = 0;
+        for (int r = 1; r <= max_rounds; ++r) used += ctrl[r] != 0;
+        counts[3] = static_cast<unsigned long long>(used);
+        if (ctrl[max_rounds] != 0) dw::status_or(status, DW_S_FOREST_ROUNDS);
+    }
+}
+
+// counts[0] += the non-loop edges (entries with col > row), counts[1] += those in the forest. A
+// block owns CAND_TILE entries, as in k_candidates: with 256 per block the two atomics of
+// 78,000 blocks on neighbouring words took 1.86 ms of the call's 5.0 at R-MAT 20.
+__global__ void __launch_bounds__(256)
+    k_forest_count(const int32_t *__restrict__ col, const int32_t *__restrict__ rows,
+                   int64_t n_rows, int64_t nnz, const uint8_t *__restrict__ forest,
+                   unsigned long long *counts) {
+    __shared__ uint32_t s_edges[4], s_forest[4];
+    const int64_t tile = blockIdx.x * static_cast<int64_t>(CAND_TILE);
+    uint32_t edge = 0, in_forest = 0;
+#pragma unroll
+    for (int k = 0; k < CAND_PER; ++k) {
+        const int64_t e = tile + k * 256 + threadIdx.x;
+        if (e < nnz) {
+            const int64_t x = rows[e], y = col[e];
+            const bool upper = entry_ok(x, y, n_rows) && y > x;
+            edge += upper;
+            in_forest += upper && forest[e];
+        }
+    }
+    const uint32_t n_edges = block_sum(edge, s_edges), n_forest = block_sum(in_forest, s_forest);
+    if (threadIdx.x == 0) {
+        if (n_edges) atomicAdd(counts, static_cast<unsigned long long>(n_edges));
+        if (n_forest) atomicAdd(counts + 1, static_cast<unsigned long long>(n_forest));
+    }
+}
+
+// The two calls of the split behind both pairs of entry points: `protect` NULL = the per-node
+// minimum rule, else the caller's flags.
+int count_impl(const char *who, const int64_t *row_ptr, const int32_t *col, int64_t n_rows,
+               int64_t nnz, uint64_t seed, const uint8_t *protect, int64_t *counts,
+               int32_t *status, void *workspace, size_t workspace_bytes, void *stream) {
+    int rc = check_sizes(who, n_rows, nnz);
+    if (rc != DW_OK) return rc;
+    DW_REQUIRE(row_ptr && (col || nnz == 0) && counts && status && workspace,
+               "%s: null pointer", who);
+    Arena a{static_cast<char *>(workspace)};
+    Bufs p;
+    rc = plan(a, n_rows, nnz, &p);
+    if (rc != DW_OK) return rc;
+    DW_REQUIRE(workspace_bytes >= a.off && reinterpret_cast<uintptr_t>(workspace) % 256 == 0,
+               "%s: workspace too small or misaligned (%zu < %zu)", who, workspace_bytes, a.off);
+    hipStream_t st = dw::as_stream(stream);
+    const uint64_t mseed = mix64(seed);
+    DW_HIP_OK(hipMemsetAsync(counts, 0, 2 * sizeof(int64_t), st), who);
+    hipLaunchKernelGGL(k_fill, dim3(grid_of(n_rows)), dim3(256), 0, st, p.minp, n_rows, NO_PRIO);
+    DW_LAUNCH_CHECK(who);
+    if (nnz == 0) return DW_OK;
+    hipLaunchKernelGGL(k_min_prio, dim3(grid_of(nnz)), dim3(256), 0, st, row_ptr, col, n_rows, nnz,
+                       mseed, p.rows, p.minp, status);
+    DW_LAUNCH_CHECK(who);
+    const dim3 tiles(static_cast<unsigned>((nnz + CAND_TILE - 1) / CAND_TILE));
+    unsigned long long *cnt = reinterpret_cast<unsigned long long *>(counts);
+    if (protect)
+        hipLaunchKernelGGL(k_candidates<ByFlag>, tiles, dim3(256), 0, st, col, p.rows, n_rows, nnz,
+                           mseed, ByFlag{protect}, p.cand0, cnt);
+    else
+        hipLaunchKernelGGL(k_candidates<ByMinimum>, tiles, dim3(256), 0, st, col, p.rows, n_rows,
+                           nnz, mseed, ByMinimum{p.minp}, p.cand0, cnt);
+    DW_LAUNCH_CHECK(who);
+    return DW_OK;
+}
+
+int split_impl(const char *who, const int64_t *row_ptr, const int32_t *col, const double *weights,
+               int64_t n_rows, int64_t nnz, uint64_t seed, const uint8_t *protect,
+               int64_t n_candidates, int64_t n_hold, int64_t *row_ptr_out, int32_t *col_out,
+               double *weights_out, int64_t *held, int32_t *status, void *workspace,
+               size_t workspace_bytes, void *stream) {
+    int rc = check_sizes(who, n_rows, nnz);
+    if (rc != DW_OK) return rc;
+    DW_REQUIRE(n_candidates >= 0 && 2 * n_candidates <= nnz && n_hold >= 0 &&
+                   n_hold <= n_candidates,
+               "%s: need 0 <= n_hold <= n_candidates <= nnz / 2 (got %lld, %lld)", who,
+               static_cast<long long>(n_hold), static_cast<long long>(n_candidates));
+    DW_REQUIRE(row_ptr && row_ptr_out && status && workspace &&
+                   (nnz == 0 || (col && col_out)) && (!weights || weights_out) &&
+                   (n_hold == 0 || held),
+               "%s: null pointer", who);
+    Arena a{static_cast<char *>(workspace)};
+    Bufs p;
+    rc = plan(a, n_rows, nnz, &p);
+    if (rc != DW_OK) return rc;
+    DW_REQUIRE(workspace_bytes >= a.off && reinterpret_cast<uintptr_t>(workspace) % 256 == 0,
+               "%s: workspace too small or misaligned (%zu < %zu)", who, workspace_bytes, a.off);
+    hipStream_t st = dw::as_stream(stream);
+    const uint64_t mseed = mix64(seed);
+    const int64_t nnz_out = nnz - 2 * n_hold;
+
+    const uint64_t *threshold = nullptr;
+    if (n_hold > 0) {   // T = the n_hold-th smallest candidate priority
+        rocprim::double_buffer<uint64_t> kb(p.cand0, p.cand1);
+        size_t tmp_bytes = 0;   // (the plan sized the storage for nnz keys: check this count's)
+        DW_HIP_OK(rocprim::radix_sort_keys(nullptr, tmp_bytes, kb,
+                                           static_cast<size_t>(n_candidates), 0, 64, st),
+                  who);
+        DW_REQUIRE(tmp_bytes <= p.tmp_bytes, "%s: sort storage %zu > planned %zu", who, tmp_bytes,
+                   p.tmp_bytes);
+        tmp_bytes = p.tmp_bytes;
+        DW_HIP_OK(rocprim::radix_sort_keys(p.tmp, tmp_bytes, kb, static_cast<size_t>(n_candidates),
+                                           0, 64, st),
+                  who);
+        threshold = kb.current() + (n_hold - 1);
+    }
+    if (protect)
+        hipLaunchKernelGGL(k_flags<ByFlag>, dim3(grid_of(nnz + 1)), dim3(256), 0, st, col, p.rows,
+                           n_rows, nnz, mseed, ByFlag{protect}, threshold, p.flags);
+    else
+        hipLaunchKernelGGL(k_flags<ByMinimum>, dim3(grid_of(nnz + 1)), dim3(256), 0, st, col,
+                           p.rows, n_rows, nnz, mseed, ByMinimum{p.minp}, threshold, p.flags);
+    DW_LAUNCH_CHECK(who);
+    size_t tmp_bytes = p.tmp_bytes;
+    DW_HIP_OK(rocprim::exclusive_scan(p.tmp, tmp_bytes, static_cast<const uint64_t *>(p.flags),
+                                      p.scan, uint64_t(0), static_cast<size_t>(nnz + 1),
+                                      rocprim::plus<uint64_t>(), st),
+              who);
+    if (nnz > 0) {
+        hipLaunchKernelGGL(k_write, dim3(grid_of(nnz)), dim3(256), 0, st, col, weights, p.rows, nnz,
+                           p.flags, p.scan, nnz_out, n_hold, col_out, weights_out, held, status);
+        DW_LAUNCH_CHECK(who);
+    }
+    hipLaunchKernelGGL(k_row_ptr, dim3(grid_of(n_rows + 1)), dim3(256), 0, st, row_ptr, n_rows, nnz,
+                       p.scan, nnz_out, n_hold, row_ptr_out, status);
+    DW_LAUNCH_CHECK(who);
+    return DW_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int dw_edge_forest_workspace_bytes(int64_t n_rows, int64_t nnz, size_t *bytes) {
+    int rc = check_sizes("dw_edge_forest_workspace_bytes", n_rows, nnz);
+    if (rc != DW_OK) return rc;
+    DW_REQUIRE(bytes, "dw_edge_forest_workspace_bytes: null pointer");
+    Arena a{nullptr};
+    ForestBufs p;
+    forest_plan(a, n_rows, nnz, &p);
+    *bytes = a.off;
+    return DW_OK;
+}
+
+int dw_edge_forest(const int64_t *row_ptr, const int32_t *col, int64_t n_rows, int64_t nnz,
+                   uint64_t seed, uint8_t *forest, int32_t *component, int64_t *counts,
+                   int32_t *status, void *workspace, size_t workspace_bytes, void *stream) {
+    int rc = check_sizes("dw_edge_forest", n_rows, nnz);
+    if (rc != DW_OK) return rc;
+    DW_REQUIRE(row_ptr && (nnz == 0 || (col && forest)) && component && counts && status &&
+                   workspace,
+               "dw_edge_forest: null pointer");
+    Arena a{static_cast<char *>(workspace)};
+    ForestBufs p;
+    forest_plan(a, n_rows, nnz, &p);
+    DW_REQUIRE(workspace_bytes >= a.off && reinterpret_cast<uintptr_t>(workspace) % 256 == 0,
+               "dw_edge_forest: workspace too small or misaligned (%zu < %zu)", workspace_bytes,
+               a.off);
+    hipStream_t st = dw::as_stream(stream);
+    const uint64_t mseed = mix64(seed);
+    const int max_rounds = forest_rounds(n_rows);
+    unsigned long long *cnt = reinterpret_cast<unsigned long long *>(counts);
+    DW_HIP_OK(hipMemsetAsync(counts, 0, 4 * sizeof(int64_t), st), "dw_edge_forest: memset");
+    const int64_t n_init = n_rows > max_rounds + 1 ? n_rows : max_rounds + 1;
+    hipLaunchKernelGGL(k_forest_init, dim3(grid_of(n_init)), dim3(256), 0, st, n_rows,
+                       max_rounds + 1, p.comp, p.parent, p.minid, p.best, p.ctrl);
+    DW_LAUNCH_CHECK("dw_edge_forest/init");
+    if (nnz > 0) {
+        DW_HIP_OK(hipMemsetAsync(forest, 0, static_cast<size_t>(nnz), st),
+                  "dw_edge_forest: memset");
+        const dim3 per_entry(grid_of(nnz)), per_row(grid_of(n_rows));
+        hipLaunchKernelGGL(k_forest_rows, per_entry, dim3(256), 0, st, row_ptr, col, n_rows, nnz,
+                           p.rows, status);
+        DW_LAUNCH_CHECK("dw_edge_forest/rows");
+        for (int r = 0; r < max_rounds; ++r) {
+            hipLaunchKernelGGL(k_comp_min, per_entry, dim3(256), 0, st, col, p.rows, n_rows, nnz,
+                               mseed, p.comp, p.ctrl + r, p.best);
+            hipLaunchKernelGGL(k_hook, per_entry, dim3(256), 0, st, col, p.rows, n_rows, nnz,
+                               mseed, p.comp, p.best, p.ctrl + r, p.parent, forest,
+                               p.ctrl + r + 1, status);
+            hipLaunchKernelGGL(k_compress, per_row, dim3(256), 0, st, n_rows, p.parent,
+                               p.ctrl + r + 1, p.comp, p.best);
+            DW_LAUNCH_CHECK("dw_edge_forest/round");
+        }
+        hipLaunchKernelGGL(k_forest_count,
+                           dim3(static_cast<unsigned>((nnz + CAND_TILE - 1) / CAND_TILE)),
+                           dim3(256), 0, st, col, p.rows, n_rows, nnz, forest, cnt);
+        DW_LAUNCH_CHECK("dw_edge_forest/count");
+    }
+    hipLaunchKernelGGL(k_comp_minid, dim3(grid_of(n_rows)), dim3(256), 0, st, n_rows, p.comp,
+                       p.minid);
+    hipLaunchKernelGGL(k_forest_labels, dim3(grid_of(n_rows)), dim3(256), 0, st, row_ptr, col,
+                       n_rows, nnz, p.comp, p.minid, p.ctrl, max_rounds, component, cnt, status);
+    DW_LAUNCH_CHECK("dw_edge_forest/labels");
+    return DW_OK;
+}
 
 int dw_edge_holdout_workspace_bytes(int64_t n_rows, int64_t nnz, size_t *bytes) {
     int rc = check_sizes("dw_edge_holdout_workspace_bytes", n_rows, nnz);
@@ -275,32 +676,8 @@ int dw_edge_holdout_workspace_bytes(int64_t n_rows, int64_t nnz, size_t *bytes) 
 int dw_edge_holdout_count(const int64_t *row_ptr, const int32_t *col, int64_t n_rows, int64_t nnz,
                           uint64_t seed, int64_t *counts, int32_t *status, void *workspace,
                           size_t workspace_bytes, void *stream) {
-    int rc = check_sizes("dw_edge_holdout_count", n_rows, nnz);
-    if (rc != DW_OK) return rc;
-    DW_REQUIRE(row_ptr && (col || nnz == 0) && counts && status && workspace,
-               "dw_edge_holdout_count: null pointer");
-    Arena a{static_cast<char *>(workspace)};
-    Bufs p;
-    rc = plan(a, n_rows, nnz, &p);
-    if (rc != DW_OK) return rc;
-    DW_REQUIRE(workspace_bytes >= a.off && reinterpret_cast<uintptr_t>(workspace) % 256 == 0,
-               "dw_edge_holdout_count: workspace too small or misaligned (%zu < %zu)",
-               workspace_bytes, a.off);
-    hipStream_t st = dw::as_stream(stream);
-    const uint64_t mseed = mix64(seed);
-    DW_HIP_OK(hipMemsetAsync(counts, 0, 2 * sizeof(int64_t), st), "dw_edge_holdout_count: memset");
-    hipLaunchKernelGGL(k_fill, dim3(grid_of(n_rows)), dim3(256), 0, st, p.minp, n_rows, NO_PRIO);
-    DW_LAUNCH_CHECK("dw_edge_holdout_count/fill");
-    if (nnz == 0) return DW_OK;
-    hipLaunchKernelGGL(k_min_prio, dim3(grid_of(nnz)), dim3(256), 0, st, row_ptr, col, n_rows, nnz,
-                       mseed, p.rows, p.minp, status);
-    DW_LAUNCH_CHECK("dw_edge_holdout_count/min");
-    hipLaunchKernelGGL(k_candidates, dim3(static_cast<unsigned>((nnz + CAND_TILE - 1) / CAND_TILE)),
-                       dim3(256), 0, st, col, p.rows, n_rows,
-                       nnz, mseed, p.minp, p.cand0,
-                       reinterpret_cast<unsigned long long *>(counts));
-    DW_LAUNCH_CHECK("dw_edge_holdout_count/candidates");
-    return DW_OK;
+    return count_impl("dw_edge_holdout_count", row_ptr, col, n_rows, nnz, seed, nullptr, counts,
+                      status, workspace, workspace_bytes, stream);
 }
 
 int dw_edge_holdout(const int64_t *row_ptr, const int32_t *col, const double *weights,
@@ -308,59 +685,30 @@ int dw_edge_holdout(const int64_t *row_ptr, const int32_t *col, const double *we
                     int64_t n_hold, int64_t *row_ptr_out, int32_t *col_out, double *weights_out,
                     int64_t *held, int32_t *status, void *workspace, size_t workspace_bytes,
                     void *stream) {
-    int rc = check_sizes("dw_edge_holdout", n_rows, nnz);
-    if (rc != DW_OK) return rc;
-    DW_REQUIRE(n_candidates >= 0 && 2 * n_candidates <= nnz && n_hold >= 0 &&
-                   n_hold <= n_candidates,
-               "dw_edge_holdout: need 0 <= n_hold <= n_candidates <= nnz / 2 (got %lld, %lld)",
-               static_cast<long long>(n_hold), static_cast<long long>(n_candidates));
-    DW_REQUIRE(row_ptr && row_ptr_out && status && workspace &&
-                   (nnz == 0 || (col && col_out)) && (!weights || weights_out) &&
-                   (n_hold == 0 || held),
-               "dw_edge_holdout: null pointer");
-    Arena a{static_cast<char *>(workspace)};
-    Bufs p;
-    rc = plan(a, n_rows, nnz, &p);
-    if (rc != DW_OK) return rc;
-    DW_REQUIRE(workspace_bytes >= a.off && reinterpret_cast<uintptr_t>(workspace) % 256 == 0,
-               "dw_edge_holdout: workspace too small or misaligned (%zu < %zu)", workspace_bytes,
-               a.off);
-    hipStream_t st = dw::as_stream(stream);
-    const uint64_t mseed = mix64(seed);
-    const int64_t nnz_out = nnz - 2 * n_hold;
+    return split_impl("dw_edge_holdout", row_ptr, col, weights, n_rows, nnz, seed, nullptr,
+                      n_candidates, n_hold, row_ptr_out, col_out, weights_out, held, status,
+                      workspace, workspace_bytes, stream);
+}
 
-    const uint64_t *threshold = nullptr;
-    if (n_hold > 0) {   // T = the n_hold-th smallest candidate priority
-        rocprim::double_buffer<uint64_t> kb(p.cand0, p.cand1);
-        size_t tmp_bytes = 0;   // (the plan sized the storage for nnz keys: check this count's)
-        DW_HIP_OK(rocprim::radix_sort_keys(nullptr, tmp_bytes, kb,
-                                           static_cast<size_t>(n_candidates), 0, 64, st),
-                  "dw_edge_holdout: candidate sort plan");
-        DW_REQUIRE(tmp_bytes <= p.tmp_bytes, "dw_edge_holdout: sort storage %zu > planned %zu",
-                   tmp_bytes, p.tmp_bytes);
-        tmp_bytes = p.tmp_bytes;
-        DW_HIP_OK(rocprim::radix_sort_keys(p.tmp, tmp_bytes, kb, static_cast<size_t>(n_candidates),
-                                           0, 64, st),
-                  "dw_edge_holdout: candidate sort");
-        threshold = kb.current() + (n_hold - 1);
-    }
-    hipLaunchKernelGGL(k_flags, dim3(grid_of(nnz + 1)), dim3(256), 0, st, col, p.rows, n_rows, nnz,
-                       mseed, p.minp, threshold, p.flags);
-    DW_LAUNCH_CHECK("dw_edge_holdout/flags");
-    size_t tmp_bytes = p.tmp_bytes;
-    DW_HIP_OK(rocprim::exclusive_scan(p.tmp, tmp_bytes, static_cast<const uint64_t *>(p.flags),
-                                      p.scan, uint64_t(0), static_cast<size_t>(nnz + 1),
-                                      rocprim::plus<uint64_t>(), st),
-              "dw_edge_holdout: scan");
-    if (nnz > 0) {
-        hipLaunchKernelGGL(k_write, dim3(grid_of(nnz)), dim3(256), 0, st, col, weights, p.rows, nnz,
-                           p.flags, p.scan, nnz_out, n_hold, col_out, weights_out, held, status);
-        DW_LAUNCH_CHECK("dw_edge_holdout/write");
-    }
-    hipLaunchKernelGGL(k_row_ptr, dim3(grid_of(n_rows + 1)), dim3(256), 0, st, row_ptr, n_rows, nnz,
-                       p.scan, nnz_out, n_hold, row_ptr_out, status);
-    DW_LAUNCH_CHECK("dw_edge_holdout/row_ptr");
-    return DW_OK;
+int dw_edge_holdout_count_protected(const int64_t *row_ptr, const int32_t *col, int64_t n_rows,
+                                    int64_t nnz, uint64_t seed, const uint8_t *protect,
+                                    int64_t *counts, int32_t *status, void *workspace,
+                                    size_t workspace_bytes, void *stream) {
+    DW_REQUIRE(protect, "dw_edge_holdout_count_protected: null pointer");
+    return count_impl("dw_edge_holdout_count_protected", row_ptr, col, n_rows, nnz, seed, protect,
+                      counts, status, workspace, workspace_bytes, stream);
+}
+
+int dw_edge_holdout_protected(const int64_t *row_ptr, const int32_t *col, const double *weights,
+                              int64_t n_rows, int64_t nnz, uint64_t seed, const uint8_t *protect,
+                              int64_t n_candidates, int64_t n_hold, int64_t *row_ptr_out,
+                              int32_t *col_out, double *weights_out, int64_t *held,
+                              int32_t *status, void *workspace, size_t workspace_bytes,
+                              void *stream) {
+    DW_REQUIRE(protect, "dw_edge_holdout_protected: null pointer");
+    return split_impl("dw_edge_holdout_protected", row_ptr, col, weights, n_rows, nnz, seed,
+                      protect, n_candidates, n_hold, row_ptr_out, col_out, weights_out, held,
+                      status, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

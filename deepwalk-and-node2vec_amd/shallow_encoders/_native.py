@@ -36,6 +36,7 @@ DW_S_BAD_TEXT = 256
 DW_S_NEG_WEIGHT = 512
 DW_S_NAN_SCORE = 1024
 DW_S_NONFINITE = 2048
+DW_S_FOREST_ROUNDS = 4096
 DW_EXACT_DEFER = 1
 DW_EXACT_ADAM = 2
 
@@ -45,7 +46,7 @@ DW_METHOD_NODE2VEC = 1
 DW_OVR_THRESHOLD = 0
 DW_OVR_TOP_K = 1
 
-ABI_VERSION = 35
+ABI_VERSION = 36
 
 _p = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -172,6 +173,13 @@ SIGNATURES = {
                                              ctypes.c_size_t, _p]),
     'dw_edge_holdout': (ctypes.c_int, [_p, _p, _p, _i64, _i64, _u64, _i64, _i64, _p, _p, _p, _p,
                                        _p, _p, ctypes.c_size_t, _p]),
+    'dw_edge_forest_workspace_bytes': (ctypes.c_int, [_i64, _i64, _szp]),
+    'dw_edge_forest': (ctypes.c_int, [_p, _p, _i64, _i64, _u64, _p, _p, _p, _p, _p,
+                                      ctypes.c_size_t, _p]),
+    'dw_edge_holdout_count_protected': (ctypes.c_int, [_p, _p, _i64, _i64, _u64, _p, _p, _p, _p,
+                                                       ctypes.c_size_t, _p]),
+    'dw_edge_holdout_protected': (ctypes.c_int, [_p, _p, _p, _i64, _i64, _u64, _p, _i64, _i64, _p,
+                                                 _p, _p, _p, _p, _p, ctypes.c_size_t, _p]),
     'dw_node_softmax_workspace_bytes': (ctypes.c_int, [_i64, _i32, _i32, _szp]),
     'dw_node_softmax': (ctypes.c_int, [_p, _i64, _i32, _p, _p, _i64, _i32, _p, _p, _p, _p,
                                        ctypes.c_size_t, _p, _p]),
@@ -337,4 +345,6 @@ def check_status(status: torch.Tensor, what: str) -> None:
         raise ValueError(f'{what}: a score is NaN (it has no rank)')
     if s & DW_S_NONFINITE:
         raise ValueError(f'{what}: a value is nan or inf')
+    if s & DW_S_FOREST_ROUNDS:
+        raise RuntimeError(f'{what}: the spanning forest did not settle in its rounds')
     raise RuntimeError(f'{what}: device status {s:#x}')

@@ -43,6 +43,7 @@ class RandomWalkDataset:
         device=None,
         holdout_ratio: float = 0.0,
         holdout_seed: int = 0,
+        holdout_protect: str = 'degree',
     ):
         """
         Args:
@@ -58,10 +59,13 @@ class RandomWalkDataset:
                 CSR-built datasets only). The walker, the vocabulary and the noise weights then
                 see the residual graph; ``full_csr``, ``heldout_edges`` and ``holdout_info`` keep
                 the rest for held-out link prediction.
+            holdout_protect: which edges the split never hides: 'degree' (every node keeps an
+                edge) or 'connected' (a spanning forest stays: the residual graph keeps the
+                full graph's connected components, node2vec §4.4's condition).
         """
         self._full_csr, self._heldout_edges, self._holdout_info = None, None, None
         if holdout_ratio:
-            graph = self._hold_out(graph, holdout_ratio, holdout_seed)
+            graph = self._hold_out(graph, holdout_ratio, holdout_seed, holdout_protect)
         self._graph = graph
         if isinstance(graph, CSRGraph):
             base_nodes = list(graph.names[1:])
@@ -93,7 +97,7 @@ class RandomWalkDataset:
         self._index = 0
         self._epoch = 0
 
-    def _hold_out(self, graph, ratio: float, seed: int) -> CSRGraph:
+    def _hold_out(self, graph, ratio: float, seed: int, protect: str = 'degree') -> CSRGraph:
         """The residual graph of ``graph`` (split on the device when the graph was built there)."""
         from shallow_encoders.graph.holdout import split_edges
         if not isinstance(graph, CSRGraph):
@@ -101,14 +105,17 @@ class RandomWalkDataset:
                              'graph_edge_list): a networkx-backed dataset cannot hide edges')
         on_device = graph.col is None and 'col' in graph._dev
         train, held, info = split_edges(graph, ratio, seed,
-                                        device=graph._dev_device if on_device else None)
+                                        device=graph._dev_device if on_device else None,
+                                        protect=protect)
+        cap = ('splitting a connected component (holdout_protect=connected)'
+               if protect == 'connected' else 'isolating a node')
         if info['n_hold'] == 0:
             raise ValueError(f'holdout_ratio={ratio} hides no edge: {info["n_want"]} wanted, '
                              f'{info["n_candidates"]} of {info["n_edges"]} edges can go without '
-                             f'isolating a node')
+                             f'{cap}')
         if info['n_hold'] < info['n_want']:
             logger.warning(f'holdout_ratio={ratio} asks for {info["n_want"]} held-out edges; only '
-                           f'{info["n_hold"]} can go without isolating a node.')
+                           f'{info["n_hold"]} can go without {cap}.')
         self._full_csr, self._heldout_edges, self._holdout_info = graph, held, info
         return train
 
@@ -126,7 +133,8 @@ class RandomWalkDataset:
 
     @property
     def holdout_info(self) -> Optional[dict]:
-        """{'n_edges', 'n_want', 'n_candidates', 'n_hold'} of the split; None without one."""
+        """{'n_edges', 'n_want', 'n_candidates', 'n_hold'} of the split (and 'n_forest',
+        'n_components' under holdout_protect=connected); None without one."""
         return self._holdout_info
 
     # ---- reference surface -------------------------------------------------------------

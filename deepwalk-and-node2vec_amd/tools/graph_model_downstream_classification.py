@@ -259,6 +259,14 @@ def heldout_edge_classification_on_device(embeddings: np.ndarray, dataset, ec) -
                          'held edges out: set datamodule.additional_parameters.holdout_ratio=<r> '
                          '(0 < r < 1; graph_rmat or graph_edge_list), for training as well')
     dev = _native.require_device(None)
+    from shallow_encoders.graph.holdout import connected_components
+    n_components = connected_components(inner.full_csr, device=dev)[1]
+    logger.info(f'Held-out link prediction: the full graph has {n_components} connected '
+                f'component(s); holdout_info={inner.holdout_info}.')
+    if n_components > 1:
+        logger.warning(f'The full graph has {n_components} connected components: node2vec '
+                       f'§4.4 splits a connected graph, so its figures are not comparable '
+                       f'one to one (the largest component is not extracted here).')
     table = torch.from_numpy(np.ascontiguousarray(embeddings, dtype=np.float32)).to(dev)
     return linkpred.heldout_edge_classification(
         table, inner.full_csr, inner.csr, inner.heldout_edges, ec.n_experiments,

@@ -54,6 +54,7 @@ extern "C" {
 #define DW_S_NEG_WEIGHT    512   /* a negative edge weight reached dw_alias_build (no table law)     */
 #define DW_S_NAN_SCORE    1024   /* a NaN score reached dw_roc_auc (it has no rank)                  */
 #define DW_S_NONFINITE    2048   /* a nan or inf value reached the embedding text writer             */
+#define DW_S_FOREST_ROUNDS 4096  /* dw_edge_forest's last allowed round still joined components      */
 
 #define DW_METHOD_DEEPWALK   0   /* random_walk_generator.py:56-72 ('deepwalk' and 'dfs')          */
 #define DW_METHOD_NODE2VEC   1   /* random_walk_generator.py:75-119                                  */
@@ -930,6 +931,41 @@ int dw_edge_holdout(const int64_t *row_ptr, const int32_t *col, const double *we
                     int64_t n_hold, int64_t *row_ptr_out, int32_t *col_out, double *weights_out,
                     int64_t *held, int32_t *status, void *workspace, size_t workspace_bytes,
                     void *stream);
+
+/* ---- minimum spanning forest, connected components, the split that keeps them ---------------
+ * dw_edge_forest: the minimum spanning forest of the non-loop edges of the same simple
+ * undirected CSR under the priorities above (distinct, so the forest is unique), by Boruvka
+ * rounds over the entries: forest uint8[nnz] = 1 on both directed entries of every forest edge,
+ * else 0; component int32[n_rows] = the smallest row of the row's connected component (a row
+ * without a non-loop edge, row 0 included, is its own); counts int64[4] (DEVICE memory) = {E_nl,
+ * n_forest, the components that hold a non-loop edge, the rounds that joined components}, so
+ * n_forest = (rows with a non-loop edge) - counts[2]. ceil(log2 n_rows) rounds always suffice
+ * and that many are launched, asynchronously; the rounds after the last that joined anything
+ * return at once. Should the last one still join components, DW_S_FOREST_ROUNDS is set and the
+ * outputs are not a forest. A neighbour out of range sets DW_S_BAD_CSR, as does an entry x -> y
+ * whose mate y -> x is missing when the forest would need it; neither is used as an index.
+ * workspace: >= dw_edge_forest_workspace_bytes(n_rows, nnz) bytes, 256-B aligned. Integer
+ * atomics only: reruns are bit-identical.
+ *
+ * dw_edge_holdout_count_protected / dw_edge_holdout_protected: dw_edge_holdout_count /
+ * dw_edge_holdout with the rule "every node protects its edge of smallest priority" replaced by
+ * protect uint8[nnz] (never NULL, nnz = 0 included): a non-loop edge is a candidate when its
+ * entries' flags are 0 (both entries of an edge must agree). With dw_edge_forest's flags the residual graph keeps every connected
+ * component of the input and no bridge is held. Everything else is as above. */
+int dw_edge_forest_workspace_bytes(int64_t n_rows, int64_t nnz, size_t *bytes);
+int dw_edge_forest(const int64_t *row_ptr, const int32_t *col, int64_t n_rows, int64_t nnz,
+                   uint64_t seed, uint8_t *forest, int32_t *component, int64_t *counts,
+                   int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+int dw_edge_holdout_count_protected(const int64_t *row_ptr, const int32_t *col, int64_t n_rows,
+                                    int64_t nnz, uint64_t seed, const uint8_t *protect,
+                                    int64_t *counts, int32_t *status, void *workspace,
+                                    size_t workspace_bytes, void *stream);
+int dw_edge_holdout_protected(const int64_t *row_ptr, const int32_t *col, const double *weights,
+                              int64_t n_rows, int64_t nnz, uint64_t seed, const uint8_t *protect,
+                              int64_t n_candidates, int64_t n_hold, int64_t *row_ptr_out,
+                              int32_t *col_out, double *weights_out, int64_t *held,
+                              int32_t *status, void *workspace, size_t workspace_bytes,
+                              void *stream);
 
 /* One pass of a multinomial logistic regression over the rows table[ids[i]], no float64 copy of
  * the features stored — what sklearn's LogisticRegression.fit / .predict compute from

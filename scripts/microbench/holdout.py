@@ -12,12 +12,18 @@ dw_roc_auc in csrc/dw_linkpred.hip) at the headline shape C3: the device-built R
            8 d + 16 + 8 B per pair (two rows, the ids, z);
   auc      dw_roc_auc on 2 * 10^7 scores against sklearn.metrics.roc_auc_score on the host's
            threads; byte model 8 + 1 B per score in, twice (the key pass and the rank pass);
+  forest   split_edges at ratio 0.5 with protect='connected' against protect='degree' in the
+           same run (same clock as `split`), dw_edge_forest alone (events around the one
+           asynchronous call), the rounds it used and, from a kernel trace of one call, each
+           round's kernel times; byte model of a round: rows, col (4 B each) and two component
+           labels (4 B each, gathered) per entry, in k_comp_min and again in k_hook;
   quality  one sge_sg_rmat20 epoch with holdout_ratio=0.5, then protocol=heldout (10
-           experiments), per noise law: the held-out AUC and accuracy.
+           experiments), per noise law and per holdout_protect rule: the held-out AUC and
+           accuracy.
 
 Each kernel's model bytes over its time are also given as a share of dw_stream_copy's rate.
 
-    python scripts/microbench/holdout.py [--part split|scores|auc|kernels|quality|all] [--json PATH]
+    python scripts/microbench/holdout.py [--part split|forest|scores|auc|kernels|quality|all] [--json PATH]
 
 One JSON line per part on stdout (and appended to --json, default profiles/holdout.jsonl).
 """
@@ -102,6 +108,84 @@ def part_split(csr, dev, path, reps=5):
           'fraction_of_stream_copy': nbytes / ms / 1e6 / copy}, path)
 
 
+def forest_call(csr, seed, dev):
+    """One dw_edge_forest call on preallocated buffers: (launch, counts, status)."""
+    import ctypes
+    d = csr.device_tensors(dev)
+    V, nnz = csr.vocab_size, csr.nnz
+    nb = ctypes.c_size_t(0)
+    _native.call('dw_edge_forest_workspace_bytes', V, nnz, ctypes.byref(nb))
+    ws = torch.empty(int(nb.value), dtype=torch.uint8, device=dev)
+    flags = torch.empty(nnz, dtype=torch.uint8, device=dev)
+    labels = torch.empty(V, dtype=torch.int32, device=dev)
+    counts = torch.zeros(4, dtype=torch.int64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def launch():
+        _native.call('dw_edge_forest', _native.ptr(d['row_ptr']), _native.ptr(d['col']), V, nnz,
+                     seed, _native.ptr(flags), _native.ptr(labels), _native.ptr(counts),
+                     _native.ptr(status), _native.ptr(ws), ws.numel(), _native.stream(dev))
+    return launch, counts, status
+
+
+def forest_kernel_trace(launch, dev):
+    """{kernel: [ms per launch, in launch order]} of one call, from torch's profiler; None when
+    it records no device kernels here."""
+    from torch.profiler import ProfilerActivity, profile
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        launch()
+        torch.cuda.synchronize(dev)
+    out = {}
+    events = sorted((ev for ev in prof.events() if 'cuda' in str(ev.device_type).lower()),
+                    key=lambda ev: ev.time_range.start)
+    for ev in events:
+        for k in ('k_forest_init', 'k_forest_rows', 'k_comp_minid', 'k_comp_min', 'k_hook',
+                  'k_compress', 'k_forest_count', 'k_forest_labels'):
+            if k in ev.name:
+                us = getattr(ev, 'device_time', None)
+                us = ev.cuda_time if us is None else us
+                out.setdefault(k, []).append(us / 1e3)
+                break
+    return out or None
+
+
+def part_forest(csr, dev, path, reps=5):
+    csr.require_simple(dev)
+    times = {'degree': [], 'connected': []}
+    for rule in times:
+        split_edges(csr, 0.5, 0, device=dev, protect=rule)                   # warm-up
+    for i in range(reps):
+        for rule in times:                                                   # alternating
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            train, held, info = split_edges(csr, 0.5, i + 1, device=dev, protect=rule)
+            torch.cuda.synchronize(dev)
+            times[rule].append((time.perf_counter() - t0) * 1e3)
+    launch, counts, status = forest_call(csr, reps, dev)
+    launch()
+    torch.cuda.synchronize(dev)
+    forest_ms = [event_ms(launch, dev) for _ in range(reps)]
+    assert int(status.item()) == 0
+    n_edges, n_forest, n_comp, rounds = counts.tolist()
+    try:
+        trace = forest_kernel_trace(launch, dev)
+    except Exception as exc:   # the profiler is an optional extra of the measurement
+        trace = None
+        print(f'no kernel trace: {exc!r}', file=sys.stderr)
+    round_bytes = 2 * 16 * csr.nnz
+    copy = stream_copy_gbps(round_bytes, dev)
+    emit({'part': 'forest', 'rows': csr.vocab_size, 'nnz': csr.nnz, 'ratio': 0.5, **info,
+          'connected_split_ms': statistics.median(times['connected']),
+          'connected_split_ms_all': times['connected'],
+          'degree_split_ms': statistics.median(times['degree']),
+          'degree_split_ms_all': times['degree'],
+          'forest_call_ms': statistics.median(forest_ms), 'forest_call_ms_all': forest_ms,
+          'rounds': rounds, 'rounds_launched': (csr.vocab_size - 1).bit_length(),
+          'n_forest_call': n_forest, 'n_components_call': n_comp,
+          'kernel_ms': trace, 'round_model_bytes': round_bytes, 'stream_copy_GBps': copy,
+          'round_model_ms_at_stream_copy': round_bytes / copy / 1e6}, path)
+
+
 def labelled_pairs(csr, dev):
     pos = linkpred.positive_edges(csr, dev)
     pos = pos[torch.randperm(pos.shape[0], device=dev)][:N_PAIRS]
@@ -171,16 +255,17 @@ def part_auc(z, labels, dev, path, reps=5):
           'fraction_of_stream_copy': nbytes / ms / 1e6 / copy}, path)
 
 
-def part_quality(path, noises=('device', 'unigram')):
+def part_quality(path, noises=('device', 'unigram'), protects=('degree', 'connected')):
     import random
 
     from tools import graph_model_downstream_classification as downstream
     from tools import train as train_tool
-    for noise in noises:
+    for noise, protect in [(n, p) for n in noises for p in protects]:
         with tempfile.TemporaryDirectory() as out:
             base = ['--config-name', 'sge_sg_rmat20', f'path.output_dir={out}',
                     f'output_dir={out}', f'train.noise={noise}', 'train.max_epochs=1',
                     'datamodule.additional_parameters.holdout_ratio=0.5',
+                    f'datamodule.additional_parameters.holdout_protect={protect}',
                     'downstream.node_classification.enable=false']
             torch.manual_seed(0)
             random.seed(0)
@@ -193,28 +278,33 @@ def part_quality(path, noises=('device', 'unigram')):
                                               'downstream.edge_classification.backend=device',
                                               f'downstream.edge_classification.scorer={scorer}'])
                 emit({'part': 'quality', 'config': 'sge_sg_rmat20', 'epochs': 1, 'noise': noise,
-                      'holdout_ratio': 0.5, 'scorer': scorer, **res, 'train_tool_s': train_s,
+                      'holdout_ratio': 0.5, 'holdout_protect': protect, 'scorer': scorer, **res,
+                      'train_tool_s': train_s,
                       'downstream_tool_s': time.perf_counter() - t0}, path)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--part', default='all',
-                    choices=['all', 'kernels', 'split', 'scores', 'auc', 'quality'])
+                    choices=['all', 'kernels', 'split', 'forest', 'scores', 'auc', 'quality'])
     ap.add_argument('--json', default=os.path.join(REPO, 'profiles', 'holdout.jsonl'))
+    ap.add_argument('--noise', default=None, choices=['device', 'unigram'],
+                    help='quality: one noise law instead of both')
     args = ap.parse_args()
     dev = torch.device('cuda', 0)
     if args.part != 'quality':
         csr = rmat_graph(SCALE, EDGES, 0, device=dev)
         if args.part in ('all', 'kernels', 'split'):
             part_split(csr, dev, args.json)
+        if args.part in ('all', 'kernels', 'forest'):
+            part_forest(csr, dev, args.json)
         if args.part in ('all', 'kernels', 'scores', 'auc'):
             z, labels = part_scores(csr, dev, args.json if args.part != 'auc' else None)
             if args.part != 'scores':
                 part_auc(z, labels, dev, args.json)
         del csr
     if args.part in ('all', 'quality'):
-        part_quality(args.json)
+        part_quality(args.json, noises=(args.noise,) if args.noise else ('device', 'unigram'))
 
 
 if __name__ == '__main__':
