@@ -25,7 +25,7 @@ ARCH = os.environ.get('DW_OFFLOAD_ARCH', 'gfx950')
 SOURCES = ['dw_abi.cpp', 'dw_host.cpp', 'dw_mt_host.cpp', 'dw_graph.hip', 'dw_walk.hip',
            'dw_sgns.hip', 'dw_sgns_shared.hip', 'dw_noise.hip', 'dw_adam.hip', 'dw_rmat.hip',
            'dw_mt.hip', 'dw_linkpred.hip', 'dw_sgd.hip', 'dw_edgelist.hip', 'dw_nodeclf.hip',
-           'dw_holdout.hip', 'dw_embtext.hip']
+           'dw_holdout.hip', 'dw_embtext.hip', 'dw_embread.hip']
 # dw_mt_host.cpp is host-only C++ (jump-ahead polynomials over GF(2), carry-less multiplies)
 # dw_linkpred.hip: its fp32 edge operators are pinned bit for bit to numpy's unfused arithmetic
 # dw_sgd.hip: its explicit-fma chain is pinned bit for bit to torch.optim.SGD on CPU fp32
@@ -33,6 +33,7 @@ EXTRA = {'dw_walk.hip': ['-ffp-contract=off'], 'dw_linkpred.hip': ['-ffp-contrac
          'dw_sgd.hip': ['-ffp-contract=off'], 'dw_mt_host.cpp': ['-x', 'c++']}
 HEADERS = [os.path.join(HERE, 'dw_common.h'), os.path.join(HERE, 'dw_ingest.h'),
            os.path.join(HERE, 'dw_strtod.h'), os.path.join(HERE, 'dw_f32text.h'),
+           os.path.join(HERE, 'dw_embread.h'),
            os.path.join(REPO, 'include', 'dw_hip.h')]
 BASE_FLAGS = ['-x', 'hip', f'--offload-arch={ARCH}', '-O3', '-fPIC', '-std=c++17',
               '-Wall', '-Wno-unused-function', '-I', os.path.join(REPO, 'include')]

@@ -17,6 +17,7 @@
 #include <string.h>
 
 #include "dw_common.h"
+#include "dw_embread.h"
 #include "dw_f32text.h"
 #include "dw_strtod.h"
 
@@ -377,6 +378,100 @@ int dw_embtext_host(const float *table, int64_t vocab_size, int32_t dim, const i
         else
             line_off[r + 1] = line_off[r] + len;
     }
+    *status |= st;
+    return DW_OK;
+}
+
+int dw_f32_token_host(const uint8_t *token, int64_t n_bytes, int32_t *kind, uint32_t *bits32) {
+    namespace er = dw::embread;
+    DW_REQUIRE(kind && bits32 && n_bytes >= 0 && (token || n_bytes == 0),
+               "dw_f32_token_host: bad arguments");
+    *kind = DW_TOKEN_BAD;
+    *bits32 = 0;
+    if (n_bytes == 0 || er::token_end(Bytes{token}, 0, n_bytes) != n_bytes) return DW_OK;
+    int64_t end = 0;
+    *kind = er::value_token(Bytes{token}, 0, n_bytes, pow5_table().w, &end, bits32);
+    return DW_OK;
+}
+
+// The host mirror of dw_embread_lines + dw_embread_parse: the same token code (dw_embread.h),
+// one line after the other.
+int dw_embread_host(const uint8_t *text, int64_t n_bytes, int32_t dim, float *table,
+                    int64_t n_rows, int64_t row0, int64_t *key_off, int64_t *key_len,
+                    int64_t *key_i64, int64_t *undecided, int64_t undecided_capacity,
+                    int64_t *counts, int64_t *err_line, int32_t *status) {
+    namespace er = dw::embread;
+    DW_REQUIRE(dim >= 1, "dw_embread_host: dim must be >= 1");
+    if (dim > er::MAX_DIM) {
+        dw::set_error("dw_embread_host: dim %d > %d is not supported", dim, er::MAX_DIM);
+        return DW_E_UNSUPPORTED;
+    }
+    DW_REQUIRE(n_bytes >= 0 && undecided_capacity >= 0 && row0 >= 0 && row0 <= n_rows,
+               "dw_embread_host: bad sizes");
+    DW_REQUIRE(counts && err_line && status && (n_bytes == 0 || text) &&
+                   (row0 == n_rows || (table && key_off && key_len && key_i64)) &&
+                   (undecided_capacity == 0 || undecided),
+               "dw_embread_host: null pointer");
+    const Bytes t{text};
+    const uint64_t *pow5 = pow5_table().w;
+    int64_t line = 0, n_undecided = 0, bad = -1;
+    int32_t st = 0;
+    for (int64_t ls = 0; ls < n_bytes; ++line) {
+        int64_t le = ls;
+        while (le < n_bytes && text[le] != '\n') ++le;
+        const int64_t next = le < n_bytes ? le + 1 : le;
+        if (row0 + line < n_rows) {
+            int64_t tokens = 0;
+            for (int64_t p = ls; p < le;) {   // the count first: a bad line stores nothing
+                if (er::is_blank(text[p])) {
+                    ++p;
+                } else {
+                    ++tokens;
+                    p = er::token_end(t, p, le);
+                }
+            }
+            if (tokens != dim + 1) {
+                st |= DW_S_BAD_TEXT;
+                if (bad < 0) bad = line;
+            } else {
+                const int64_t row = row0 + line;
+                int64_t j = 0;
+                for (int64_t p = ls; p < le;) {
+                    if (er::is_blank(text[p])) {
+                        ++p;
+                        continue;
+                    }
+                    int64_t e = p;
+                    if (j == 0) {
+                        key_i64[row] = er::key_token(t, p, le, &e);
+                        key_off[row] = p;
+                        key_len[row] = e - p;
+                        if (key_i64[row] < 0) st |= DW_S_TEXT_KEY;
+                    } else {
+                        uint32_t bits = 0;
+                        const int kind = er::value_token(t, p, le, pow5, &e, &bits);
+                        memcpy(table + row * dim + (j - 1), &bits, 4);
+                        if (kind == er::TOKEN_UNDECIDED) {
+                            if (n_undecided < undecided_capacity) {
+                                int64_t *u = undecided + er::UNDECIDED_WORDS * n_undecided;
+                                u[0] = row;
+                                u[1] = j - 1;
+                                u[2] = p;
+                                u[3] = e - p;
+                            }
+                            ++n_undecided;
+                        }
+                    }
+                    ++j;
+                    p = e;
+                }
+            }
+        }
+        ls = next;
+    }
+    counts[0] = line;
+    counts[1] = n_undecided;
+    *err_line = bad;
     *status |= st;
     return DW_OK;
 }

@@ -1,6 +1,7 @@
 // Exact decimal-to-double conversion in integer arithmetic, shared by the weighted edge-list
 // parser (dw_edgelist.hip: the kernel) and dw_weight_token_host (dw_host.cpp: the same code on
-// the host, for CPU tests). Not part of the ABI. Restated in tests/strtod_ref.py.
+// the host, for CPU tests), and by the embedding text reader (dw_embread.h), which rounds the
+// double on to float32 (f32_from_f64_bits). Not part of the ABI. Restated in tests/strtod_ref.py.
 //
 // The method is Eisel-Lemire (Lemire, "Number parsing at a gigabyte per second", 2021): a decimal
 // significand w < 2^64 and a power of ten q give the double nearest w * 10^q from one or two
@@ -162,6 +163,34 @@ __host__ __device__ __forceinline__ bool scan_bits(const Scan &s,
     }
     *bits = b | (s.neg ? 1ull << 63 : 0ull);
     return true;
+}
+
+// numpy.float32(x) of the double with these bits, in integer arithmetic: the 53-bit significand
+// is cut to 24 bits — fewer below 2^-126, where the result is a subnormal counted in units of
+// 2^-149 — and rounded to nearest, ties to even. A carry out of the significand moves into the
+// exponent field by itself, so the round-up into FLT_MIN and into a power of two need no case of
+// their own; from 2^128 - 2^103 on the result is inf. No hardware f64 -> f32 convert: its
+// subnormal results depend on the kernel's denormal mode.
+__host__ __device__ __forceinline__ uint32_t f32_from_f64_bits(uint64_t b) {
+    const uint32_t sign = static_cast<uint32_t>(b >> 63) << 31;
+    const int32_t e = static_cast<int32_t>((b >> 52) & 0x7FFu);
+    const uint64_t m = b & ((1ull << 52) - 1);
+    if (e == 0x7FF) return sign | (m ? 0x7FC00000u : 0x7F800000u);
+    if (e == 0) return sign;                       // zero, or below 2^-1022
+    const uint64_t sig = m | (1ull << 52);         // the value is sig * 2^(e - 1075)
+    int32_t shift = 29, field = e - 1023 + 127;    // float32's exponent field, if normal
+    if (field <= 0) {                              // subnormal: units of 2^-149, field 0
+        shift += 1 - field;
+        field = 0;
+        if (shift > 54) return sign;               // below 2^-150: under half a unit
+    } else {
+        --field;                                   // (the significand's top bit adds it back)
+    }
+    const uint64_t keep = sig >> shift, rem = sig & ((1ull << shift) - 1);
+    const uint64_t half = 1ull << (shift - 1);
+    const uint64_t up = (rem > half || (rem == half && (keep & 1u))) ? 1u : 0u;
+    const uint64_t r = (static_cast<uint64_t>(field) << 23) + keep + up;
+    return sign | (r >= 0x7F800000u ? 0x7F800000u : static_cast<uint32_t>(r));
 }
 
 }  // namespace strtod

@@ -37,6 +37,7 @@ DW_S_NEG_WEIGHT = 512
 DW_S_NAN_SCORE = 1024
 DW_S_NONFINITE = 2048
 DW_S_FOREST_ROUNDS = 4096
+DW_S_TEXT_KEY = 8192
 DW_EXACT_DEFER = 1
 DW_EXACT_ADAM = 2
 
@@ -46,7 +47,7 @@ DW_METHOD_NODE2VEC = 1
 DW_OVR_THRESHOLD = 0
 DW_OVR_TOP_K = 1
 
-ABI_VERSION = 36
+ABI_VERSION = 37
 
 _p = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -96,6 +97,13 @@ SIGNATURES = {
                                         ctypes.c_size_t, _p]),
     'dw_embtext_write': (ctypes.c_int, [_p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _i64, _i64,
                                         _p, _i64, _p, _p]),
+    'dw_embread_host': (ctypes.c_int, [_p, _i64, _i32, _p, _i64, _i64, _p, _p, _p, _p, _i64, _p,
+                                       _p, _p]),
+    'dw_f32_token_host': (ctypes.c_int, [_p, _i64, _p, _p]),
+    'dw_embread_workspace_bytes': (ctypes.c_int, [_i64, _szp]),
+    'dw_embread_lines': (ctypes.c_int, [_p, _i64, _p, _i64, _p, _p, _p, ctypes.c_size_t, _p]),
+    'dw_embread_parse': (ctypes.c_int, [_p, _i64, _p, _i64, _i32, _p, _p, _i64, _i64, _p, _p, _p,
+                                        _p, _i64, _p, _p, _p, _p]),
     'dw_edges_canonical': (ctypes.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _p, _p, _p, _p,
                                           ctypes.c_size_t, _p]),
     'dw_csr_from_edges_loops': (ctypes.c_int, [_p, _p, _i64, _i64, _p, _p, _p, _p, _p,

@@ -23,6 +23,9 @@ MI355X additions (all optional, defaulted, so reference configs load as they are
                           from the reference's negatives per pair
   export.*                tools/export_embeddings.py: the table, path, key style and device of
                           the word2vec-text export (ExportConfig)
+  downstream.embeddings_path     a word2vec text file whose table the downstream tool scores
+                          instead of the checkpoint's (any program's .emb output)
+  downstream.embeddings_missing  'error' | 'zero': vocabulary rows that file does not hold
 ``_target_: torch.optim.Adam`` instantiates the HIP Adam and ``_target_: torch.optim.SGD`` the HIP
 SGD (word2vec/optim.py, same math).
 """
@@ -270,6 +273,13 @@ class GraphDownstreamTaskConfig:
         default_factory=GraphDownstreamNodeClassificationConfig)
     edge_classification: GraphDownstreamEdgeClassificationConfig = field(
         default_factory=GraphDownstreamEdgeClassificationConfig)
+    embeddings_path: Optional[str] = None   # a word2vec text file instead of the checkpoint
+    embeddings_missing: str = 'error'       # 'error' | 'zero' (embeddings_io.align_word2vec)
+
+    def __post_init__(self):
+        if self.embeddings_missing not in ('error', 'zero'):
+            raise ValueError(f'downstream.embeddings_missing must be "error" or "zero", got '
+                             f'{self.embeddings_missing!r}')
 
 
 @dataclass

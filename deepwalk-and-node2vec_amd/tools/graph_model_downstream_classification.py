@@ -27,6 +27,10 @@ logistic regression, micro- and macro-F1 under ``downstream.node_classification.
 ``holdout_ratio`` > 0) replaces the in-sample edge task by node2vec §4.4's: the edges the dataset
 hid before training are ranked against non-edges, reported as ``edge_auc`` (exact ROC AUC),
 ``edge_auc_std``, ``edge_accuracy`` and ``edge_best``.
+``downstream.embeddings_path=<file>`` scores a word2vec text file (this project's export, the
+node2vec or DeepWalk reference programs' output, gensim's) instead of the checkpoint: the file's
+rows are laid out by the dataset's vocabulary, ``downstream.embeddings_missing=zero`` lets nodes
+the file does not hold stay zero rows. With a device backend the HIP reader parses it.
 Only the labelled vertices are classified: a ``graph_edge_list`` dataset's label file may cover
 a part of the nodes.
 """
@@ -125,7 +129,7 @@ def node_classification_on_device(embeddings: np.ndarray, dataset, nc) -> Dict[s
         logger.info(f'Dataset info: {len(rows)} labelled nodes, {len(classes)} labels, '
                     f'd={embeddings.shape[1]}.')
         dev = _native.require_device(None)
-        table = torch.from_numpy(np.ascontiguousarray(embeddings, dtype=np.float32)).to(dev)
+        table = _device_table(embeddings, dev)
         micro, macro, best = nodeclf.node_multilabel_device(
             table, rows, masks, nc.instantiate_split_algorithm(), nc.n_experiments,
             classifier_params=nc.classifier_params, rule=nc.prediction, device=dev,
@@ -140,7 +144,7 @@ def node_classification_on_device(embeddings: np.ndarray, dataset, nc) -> Dict[s
     y = np.asarray(y, dtype=np.float32)   # the host path's label dtype (the splits see it)
     logger.info(f'Dataset info: {len(rows)} labelled nodes, d={embeddings.shape[1]}.')
     dev = _native.require_device(None)
-    table = torch.from_numpy(np.ascontiguousarray(embeddings, dtype=np.float32)).to(dev)
+    table = _device_table(embeddings, dev)
     mean, best, confusion = nodeclf.node_classification_device(
         table, rows, y, nc.instantiate_split_algorithm(), nc.n_experiments,
         classifier_params=nc.classifier_params, device=dev)
@@ -240,7 +244,7 @@ def edge_classification_on_device(embeddings: np.ndarray, graph, ec) -> Tuple[fl
     from shallow_encoders.graph import linkpred
     from shallow_encoders.graph.random_walk_generator import _csr_of
     dev = _native.require_device(None)
-    table = torch.from_numpy(np.ascontiguousarray(embeddings, dtype=np.float32)).to(dev)
+    table = _device_table(embeddings, dev)
     return linkpred.edge_classification_device(
         table, _csr_of(graph), ec.train_ratio, ec.n_experiments, ec.operator_name,
         classifier_params=ec.classifier_params, device=dev)
@@ -267,10 +271,49 @@ def heldout_edge_classification_on_device(embeddings: np.ndarray, dataset, ec) -
         logger.warning(f'The full graph has {n_components} connected components: node2vec '
                        f'§4.4 splits a connected graph, so its figures are not comparable '
                        f'one to one (the largest component is not extracted here).')
-    table = torch.from_numpy(np.ascontiguousarray(embeddings, dtype=np.float32)).to(dev)
+    table = _device_table(embeddings, dev)
     return linkpred.heldout_edge_classification(
         table, inner.full_csr, inner.csr, inner.heldout_edges, ec.n_experiments,
         ec.operator_name, classifier_params=ec.classifier_params, scorer=ec.scorer, device=dev)
+
+
+def _device_table(embeddings, dev):
+    """The float32 table on ``dev``: a checkpoint's numpy array, or a tensor a file was read to."""
+    import torch
+    if isinstance(embeddings, torch.Tensor):
+        return embeddings.to(device=dev, dtype=torch.float32).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(embeddings, dtype=np.float32)).to(dev)
+
+
+def _host_table(embeddings) -> np.ndarray:
+    return embeddings if isinstance(embeddings, np.ndarray) else embeddings.cpu().numpy()
+
+
+def load_file_embeddings(cfg, dataset):
+    """``downstream.embeddings_path``: the table of a word2vec text file (this project's export,
+    the node2vec or DeepWalk reference programs', gensim's) laid out by the dataset's vocabulary
+    (embeddings_io.align_word2vec: keys as export_embeddings.py writes them, ids first, then
+    vocabulary tokens). The HIP reader parses it when a GPU is visible and a device backend is
+    chosen (the table then stays on the GPU), the same code on the host otherwise."""
+    import torch
+    from shallow_encoders.word2vec.embeddings_io import align_word2vec, read_word2vec_format
+    ds = cfg.downstream
+    nc, ec = ds.node_classification, ds.edge_classification
+    on_device = torch.cuda.is_available() and (
+        (nc.enable and nc.backend == 'device') or
+        (ec.enable and (ec.backend == 'device' or ec.protocol == 'heldout')))
+    read = read_word2vec_format(ds.embeddings_path, device='cuda' if on_device else None)
+    vocab = getattr(getattr(dataset, 'dataset', None), 'csr', None) or dataset.vocab
+    try:
+        emb = align_word2vec(read, vocab, missing=ds.embeddings_missing, style='id')
+    except ValueError as by_id:
+        try:
+            emb = align_word2vec(read, vocab, missing=ds.embeddings_missing, style='token')
+        except ValueError:
+            raise by_id from None
+    logger.info(f'Read {read.n} x {read.d} embeddings from "{ds.embeddings_path}" '
+                f'({"the GPU" if on_device else "the host"}).')
+    return emb if on_device else np.asarray(emb)
 
 
 def load_input_embeddings(cfg, dataset, checkpoint_path: str) -> np.ndarray:
@@ -304,7 +347,10 @@ def main(argv=None) -> Dict[str, float]:
     dataset = cfg.datamodule.instantiate_dataset()
     out, ds, exp = cfg.path.output_dir, cfg.datamodule.dataset_name, cfg.train.experiment
     ckpt = conventions.get_checkpoint_path(out, ds, exp, cfg.analysis.checkpoint)
-    emb = load_input_embeddings(cfg, dataset, ckpt)
+    if cfg.downstream.embeddings_path is not None:
+        emb = load_file_embeddings(cfg, dataset)
+    else:
+        emb = load_input_embeddings(cfg, dataset, ckpt)
     analysis_dir = conventions.get_analysis_experiment_path(out, ds, exp)
     Path(analysis_dir).mkdir(parents=True, exist_ok=True)
     result: Dict[str, float] = {}
@@ -317,7 +363,7 @@ def main(argv=None) -> Dict[str, float]:
         plot = os.path.join(analysis_dir, 'downstream-node-classification.jpg') \
             if nc.visualize else None
         result['node_accuracy'], result['node_best'] = node_classification(
-            emb, dataset.vocab.get_itos(), dataset.labels, nc.instantiate_split_algorithm(),
+            _host_table(emb), dataset.vocab.get_itos(), dataset.labels, nc.instantiate_split_algorithm(),
             nc.n_experiments, features=dataset.features if dataset.has_features else None,
             classifier_params=nc.classifier_params, plot_path=plot)
     ec = cfg.downstream.edge_classification
@@ -328,7 +374,7 @@ def main(argv=None) -> Dict[str, float]:
             emb, dataset.graph, ec)
     elif ec.enable:
         result['edge_accuracy'], result['edge_best'] = edge_classification(
-            emb, dataset.graph, dataset.vocab.get_stoi(), ec.train_ratio, ec.n_experiments,
+            _host_table(emb), dataset.graph, dataset.vocab.get_stoi(), ec.train_ratio, ec.n_experiments,
             ec.operator_name, classifier_params=ec.classifier_params)
     print(' '.join(f'{k}={100 * v:.2f}%' for k, v in result.items()), flush=True)
     return result

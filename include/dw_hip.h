@@ -55,6 +55,7 @@ extern "C" {
 #define DW_S_NAN_SCORE    1024   /* a NaN score reached dw_roc_auc (it has no rank)                  */
 #define DW_S_NONFINITE    2048   /* a nan or inf value reached the embedding text writer             */
 #define DW_S_FOREST_ROUNDS 4096  /* dw_edge_forest's last allowed round still joined components      */
+#define DW_S_TEXT_KEY     8192   /* the embedding text reader met a key that is no plain integer    */
 
 #define DW_METHOD_DEEPWALK   0   /* random_walk_generator.py:56-72 ('deepwalk' and 'dfs')          */
 #define DW_METHOD_NODE2VEC   1   /* random_walk_generator.py:75-119                                  */
@@ -306,6 +307,65 @@ int dw_embtext_write(const float *table, int64_t vocab_size, int32_t dim, const 
                      const int64_t *key_off, const uint64_t *tab, const int64_t *line_off,
                      int64_t r0, int64_t r1, uint8_t *out, int64_t capacity, int32_t *status,
                      void *stream);
+
+/* ---- Word2vec text to embeddings (embeddings_io.read_word2vec_format), the way back: text[0,
+ * n_bytes) (uint8, at any alignment; no read goes past n_bytes or in front of text) is the body
+ * of a word2vec text file, or a run of whole lines of it — the caller reads the "<n> <d>" header.
+ * Lines end in '\n'; the last line may lack it. A line's tokens are its maximal runs of bytes
+ * other than space, \t, \v, \f and \r (what bytes.split() splits on: a '\r' that closes a line is
+ * dropped). Line l of the text is row row0 + l of the outputs; it holds a key and dim value
+ * tokens:
+ *   - key_off, key_len (int64 [n_rows]): the key's byte span in text; key_i64 (int64 [n_rows]):
+ *     its value where the key is 1 to 18 decimal digits with no sign and no leading zero but "0"
+ *     itself (str(value) gives the bytes back), else -1, and DW_S_TEXT_KEY is set;
+ *   - value token j goes to table[row, j] (float32 [n_rows, dim]) as numpy.float32(float(token)):
+ *     the double nearest the decimal (dw_edgelist_parse_weighted's grammar and conversion over
+ *     pow5), then that double rounded to float32, ties to even, in integer arithmetic — subnormal
+ *     results, the round-up into FLT_MIN, +-inf from 2^128 - 2^103 on, +-0. nan, inf and infinity,
+ *     in any letter case and with an optional sign, give 0x7FC00000 / 0x7F800000 with the sign
+ *     bit. Every other token — one the conversion cannot decide, one of more than 64 bytes, one
+ *     outside the grammar ("1_0", "0x10", "1e12345", "abc") — is undecided: 0.0 in the table and
+ *     an entry (row, column, byte offset, byte length) in undecided (int64 [4
+ *     undecided_capacity], in no particular order; entries past the capacity are dropped but
+ *     counted) for the host's float() to convert or refuse.
+ * A line whose token count is not dim + 1 (an empty or all-blank one included) sets
+ * DW_S_BAD_TEXT and lowers *err_line (int64, -1 = none) to the smallest such 0-based line of the
+ * text; nothing of it is stored. counts (int64 [2]): lines of the text, undecided tokens. dim >
+ * 512 returns DW_E_UNSUPPORTED before any launch. Every output is a pure function of the input
+ * (integer atomics only: the undecided counter, the error line, the status word). */
+
+/* Host only (no device; every pointer is host memory): both passes below in one entry point, the
+ * CPU path of read_word2vec_format and the kernels' mirror for tests. Lines behind row n_rows - 1
+ * are counted, not parsed. */
+int dw_embread_host(const uint8_t *text, int64_t n_bytes, int32_t dim, float *table,
+                    int64_t n_rows, int64_t row0, int64_t *key_off, int64_t *key_len,
+                    int64_t *key_i64, int64_t *undecided, int64_t undecided_capacity,
+                    int64_t *counts, int64_t *err_line, int32_t *status);
+
+/* Host only: the reader's value-token conversion on token[0, n_bytes) (a testing aid). *kind =
+ * DW_TOKEN_BAD (empty, or it holds a blank), DW_TOKEN_DECIDED (*bits32 = the float32's bits) or
+ * DW_TOKEN_UNDECIDED. */
+int dw_f32_token_host(const uint8_t *token, int64_t n_bytes, int32_t *kind, uint32_t *bits32);
+
+int dw_embread_workspace_bytes(int64_t n_bytes, size_t *bytes);
+
+/* Pass 1, the line index: line_off (device int64 [capacity + 1]) = the byte offsets of the line
+ * starts, and the text's end behind the last line; entries of lines past capacity are not
+ * written. Sets counts[0] = lines (compare it with the header's n before pass 2), counts[1] = 0
+ * and *err_line = -1. */
+int dw_embread_lines(const uint8_t *text, int64_t n_bytes, int64_t *line_off, int64_t capacity,
+                     int64_t *counts, int64_t *err_line, void *workspace, size_t workspace_bytes,
+                     void *stream);
+
+/* Pass 2, the tokens of lines [0, n_lines) of pass 1's line_off (n_lines <= its capacity, row0 +
+ * n_lines <= n_rows; pow5: device uint64 [1302], the words of dw_pow5_table): table, key_off,
+ * key_len, key_i64 at rows row0 .. row0 + n_lines - 1, the undecided entries, counts[1], *err_line
+ * and the status bits above. */
+int dw_embread_parse(const uint8_t *text, int64_t n_bytes, const int64_t *line_off,
+                     int64_t n_lines, int32_t dim, const uint64_t *pow5, float *table,
+                     int64_t n_rows, int64_t row0, int64_t *key_off, int64_t *key_len,
+                     int64_t *key_i64, int64_t *undecided, int64_t undecided_capacity,
+                     int64_t *counts, int64_t *err_line, int32_t *status, void *stream);
 
 /* Raw edges (src, dst int64 [n_edges], ids in [0, 2^id_bits), id_bits <= 60: others set
  * DW_S_BAD_INDEX; weights float64 [n_edges] or NULL) to their canonical form: node_ids int64
