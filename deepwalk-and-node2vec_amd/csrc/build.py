@@ -25,7 +25,7 @@ ARCH = os.environ.get('DW_OFFLOAD_ARCH', 'gfx950')
 SOURCES = ['dw_abi.cpp', 'dw_host.cpp', 'dw_mt_host.cpp', 'dw_graph.hip', 'dw_walk.hip',
            'dw_sgns.hip', 'dw_sgns_shared.hip', 'dw_noise.hip', 'dw_adam.hip', 'dw_rmat.hip',
            'dw_mt.hip', 'dw_linkpred.hip', 'dw_sgd.hip', 'dw_edgelist.hip', 'dw_nodeclf.hip',
-           'dw_holdout.hip', 'dw_embtext.hip', 'dw_embread.hip']
+           'dw_holdout.hip', 'dw_embtext.hip', 'dw_embread.hip', 'dw_cluster.hip']
 # dw_mt_host.cpp is host-only C++ (jump-ahead polynomials over GF(2), carry-less multiplies)
 # dw_linkpred.hip: its fp32 edge operators are pinned bit for bit to numpy's unfused arithmetic
 # dw_sgd.hip: its explicit-fma chain is pinned bit for bit to torch.optim.SGD on CPU fp32

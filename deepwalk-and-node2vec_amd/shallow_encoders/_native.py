@@ -47,7 +47,7 @@ DW_METHOD_NODE2VEC = 1
 DW_OVR_THRESHOLD = 0
 DW_OVR_TOP_K = 1
 
-ABI_VERSION = 37
+ABI_VERSION = 38
 
 _p = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -194,6 +194,14 @@ SIGNATURES = {
     'dw_node_ovr_workspace_bytes': (ctypes.c_int, [_i64, _i32, _i32, _szp]),
     'dw_node_ovr': (ctypes.c_int, [_p, _i64, _i32, _p, _p, _i64, _i32, _p, _i32, _p, _p, _p,
                                    ctypes.c_size_t, _p, _p]),
+    'dw_kmeans_step_workspace_bytes': (ctypes.c_int, [_i64, _i32, _i32, _szp]),
+    'dw_kmeans_step': (ctypes.c_int, [_p, _i64, _i32, _p, _i64, _p, _i32, _p, _p, _p, _p,
+                                      ctypes.c_size_t, _p, _p]),
+    'dw_kmeans_seed_workspace_bytes': (ctypes.c_int, [_i64, _szp]),
+    'dw_kmeans_seed': (ctypes.c_int, [_p, _i64, _i32, _p, _i64, _i32, _u64, _p, _p, _p,
+                                      ctypes.c_size_t, _p, _p]),
+    'dw_partition_counts': (ctypes.c_int, [_p, _i32, _p, _i32, _i64, _p, _p, _p]),
+    'dw_modularity_counts': (ctypes.c_int, [_p, _p, _i64, _i64, _p, _i32, _p, _p, _p]),
     'dw_embedding_renorm_workspace_bytes': (ctypes.c_int, [_i64, _i64, _szp]),
     'dw_embedding_renorm': (ctypes.c_int, [_p, _i64, _i32, _p, _i64, _f64, _p, ctypes.c_size_t,
                                            _p, _p]),

@@ -267,12 +267,44 @@ class GraphDownstreamEdgeClassificationConfig:
 
 
 @dataclass
+class GraphDownstreamClusteringConfig:
+    """k-means communities of the embeddings (node2vec §4.1; a departure: the reference has no
+    clustering task), shallow_encoders/graph/cluster.py."""
+    enable: bool = False
+    # 0: the number of label classes (a dataset without labels must name it)
+    n_clusters: int = 0
+    n_init: int = 1
+    max_iter: int = 100
+    seed: int = 0
+    # 'device': the fp32 table stays in HBM (dw_kmeans_step); 'host': the same loop in numpy
+    backend: str = 'device'
+
+    def __post_init__(self):
+        if self.backend not in ('host', 'device'):
+            raise ValueError(f'downstream.clustering.backend must be "host" or "device", got '
+                             f'{self.backend!r}')
+        if isinstance(self.n_clusters, bool) or not isinstance(self.n_clusters, int) \
+                or not 0 <= self.n_clusters <= 1024:
+            raise ValueError(f'downstream.clustering.n_clusters must be an integer in [0, 1024] '
+                             f'(0: the number of label classes), got {self.n_clusters!r}')
+        if not isinstance(self.n_init, int) or self.n_init < 1:
+            raise ValueError(f'downstream.clustering.n_init must be >= 1, got {self.n_init!r}')
+        if not isinstance(self.max_iter, int) or self.max_iter < 1:
+            raise ValueError(f'downstream.clustering.max_iter must be >= 1, got '
+                             f'{self.max_iter!r}')
+        if not isinstance(self.seed, int) or self.seed < 0:
+            raise ValueError(f'downstream.clustering.seed must be >= 0, got {self.seed!r}')
+
+
+@dataclass
 class GraphDownstreamTaskConfig:
     checkpoint: str = 'last.ckpt'
     node_classification: GraphDownstreamNodeClassificationConfig = field(
         default_factory=GraphDownstreamNodeClassificationConfig)
     edge_classification: GraphDownstreamEdgeClassificationConfig = field(
         default_factory=GraphDownstreamEdgeClassificationConfig)
+    clustering: GraphDownstreamClusteringConfig = field(
+        default_factory=GraphDownstreamClusteringConfig)
     embeddings_path: Optional[str] = None   # a word2vec text file instead of the checkpoint
     embeddings_missing: str = 'error'       # 'error' | 'zero' (embeddings_io.align_word2vec)
 

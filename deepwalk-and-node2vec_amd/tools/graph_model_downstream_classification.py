@@ -33,6 +33,12 @@ rows are laid out by the dataset's vocabulary, ``downstream.embeddings_missing=z
 the file does not hold stay zero rows. With a device backend the HIP reader parses it.
 Only the labelled vertices are classified: a ``graph_edge_list`` dataset's label file may cover
 a part of the nodes.
+``downstream.clustering.enable=true`` adds the third task of the DeepWalk / node2vec papers
+(a departure: the reference has none): k-means communities of the embeddings
+(shallow_encoders/graph/cluster.py; ``backend=device`` keeps the fp32 table on the GPU), reported
+as ``cluster_inertia``, ``cluster_modularity`` (structural, needs no labels) and
+``cluster_iterations``, and with one label per node ``cluster_nmi`` and ``cluster_ari`` against
+the labels over the labelled nodes.
 """
 import argparse
 import logging
@@ -277,6 +283,69 @@ def heldout_edge_classification_on_device(embeddings: np.ndarray, dataset, ec) -
         ec.operator_name, classifier_params=ec.classifier_params, scorer=ec.scorer, device=dev)
 
 
+def clustering(embeddings, dataset, cc) -> Dict[str, float]:
+    """``downstream.clustering``: k-means communities of the input embeddings (row 0 skipped;
+    shallow_encoders/graph/cluster.py), scored without labels by the structural modularity of the
+    graph's CSR and, where the dataset has one label per node, by NMI and ARI against the labels
+    over the labelled nodes. ``n_clusters=0`` takes the number of label classes."""
+    import torch
+    from shallow_encoders.graph import cluster
+    from shallow_encoders.graph.random_walk_generator import _csr_of
+    if is_multilabel(dataset):
+        raise ValueError('downstream.clustering compares one label per node: this dataset is '
+                         'multi-label (NMI and ARI are not defined for label sets)')
+    inner = getattr(dataset, 'dataset', dataset)
+    rows, y = None, None
+    if not dataset.has_labels:
+        pass
+    elif hasattr(inner, 'label_arrays'):
+        rows, y, _ = inner.label_arrays()
+    else:
+        itos, labels = dataset.vocab.get_itos(), dataset.labels
+        rows = [i for i, v in enumerate(itos[1:], start=1) if v in labels]
+        y = labels_to_integers([labels[itos[i]] for i in rows])
+    if rows is not None and len(rows) == 0:
+        rows, y = None, None
+    K = cc.n_clusters
+    if K == 0:
+        if y is None:
+            raise ValueError('downstream.clustering.n_clusters=0 takes the number of label '
+                             'classes: this dataset has no labels, name n_clusters')
+        K = len(set(int(c) for c in y))
+    V = embeddings.shape[0]
+    csr = getattr(inner, 'csr', None) or _csr_of(dataset.graph)
+    ids = np.arange(1, V, dtype=np.int64)
+    if cc.backend == 'device':
+        from shallow_encoders import _native
+        dev = _native.require_device(None)
+        table = _device_table(embeddings, dev)
+        labels, _, inertia, n_iter = cluster.kmeans(
+            table, torch.from_numpy(ids).to(dev), K, n_init=cc.n_init, max_iter=cc.max_iter,
+            seed=cc.seed, device=dev)
+        full = torch.cat([torch.full((1,), -1, dtype=torch.int64, device=dev), labels])
+    else:
+        labels, _, inertia, n_iter = cluster.kmeans(
+            np.ascontiguousarray(_host_table(embeddings), dtype=np.float32), ids, K,
+            n_init=cc.n_init, max_iter=cc.max_iter, seed=cc.seed)
+        full = np.concatenate([[-1], labels])
+    result = {'cluster_inertia': inertia, 'cluster_modularity': cluster.modularity(csr, full, K),
+              'cluster_iterations': float(n_iter)}
+    if y is not None:
+        rows = np.asarray(rows, dtype=np.int64)
+        truth = np.asarray(y, dtype=np.int64)
+        if cc.backend == 'device':
+            found = full[torch.from_numpy(rows).to(full.device)]
+            truth = torch.from_numpy(truth).to(full.device)
+        else:
+            found = full[rows]
+        table = cluster.contingency(truth, found)
+        result['cluster_nmi'] = cluster.nmi_from_table(table)
+        result['cluster_ari'] = cluster.ari_from_table(table)
+    logger.info('Clustering: ' + ', '.join(f'{k}={v:.6g}' for k, v in result.items())
+                + f' (K={K}, {V - 1} nodes).')
+    return result
+
+
 def _device_table(embeddings, dev):
     """The float32 table on ``dev``: a checkpoint's numpy array, or a tensor a file was read to."""
     import torch
@@ -301,7 +370,8 @@ def load_file_embeddings(cfg, dataset):
     nc, ec = ds.node_classification, ds.edge_classification
     on_device = torch.cuda.is_available() and (
         (nc.enable and nc.backend == 'device') or
-        (ec.enable and (ec.backend == 'device' or ec.protocol == 'heldout')))
+        (ec.enable and (ec.backend == 'device' or ec.protocol == 'heldout')) or
+        (ds.clustering.enable and ds.clustering.backend == 'device'))
     read = read_word2vec_format(ds.embeddings_path, device='cuda' if on_device else None)
     vocab = getattr(getattr(dataset, 'dataset', None), 'csr', None) or dataset.vocab
     try:
@@ -376,7 +446,12 @@ def main(argv=None) -> Dict[str, float]:
         result['edge_accuracy'], result['edge_best'] = edge_classification(
             _host_table(emb), dataset.graph, dataset.vocab.get_stoi(), ec.train_ratio, ec.n_experiments,
             ec.operator_name, classifier_params=ec.classifier_params)
-    print(' '.join(f'{k}={100 * v:.2f}%' for k, v in result.items()), flush=True)
+    cc = cfg.downstream.clustering
+    scores = dict(result)
+    if cc.enable:
+        result.update(clustering(emb, dataset, cc))
+    print(' '.join([f'{k}={100 * v:.2f}%' for k, v in scores.items()] +
+                   [f'{k}={v:.6g}' for k, v in result.items() if k not in scores]), flush=True)
     return result
 
 

@@ -1074,6 +1074,72 @@ int dw_node_ovr(const float *table, int64_t vocab_size, int32_t dim, const int64
                 int32_t rule, double *out, uint64_t *pred, void *workspace,
                 size_t workspace_bytes, int32_t *status, void *stream);
 
+/* One Lloyd pass of k-means over the rows table[ids[i]], no float64 copy of the features stored
+ * (node2vec section 4.1 clusters the embeddings; a departure: the reference has no clustering
+ * task). centroids double[n_clusters, dim] (DEVICE memory), ids int64[n]. Per sample, with x the
+ * fp32 row widened exactly to float64: s_k = ||c_k||^2 - 2 x . c_k, label = argmin_k s_k (ties
+ * to the lowest k), inertia term ||x||^2 + s_label. labels_out int32[n]; prev_labels int32[n] or
+ * NULL. out double[K (dim + 1) + 2], K = n_clusters: [k * (dim + 1) + j] = the sum of x_j over
+ * cluster k's members for j < dim and the member count at j = dim, then the summed inertia, then
+ * the number of samples whose label differs from prev_labels[i] (n when prev_labels is NULL).
+ * Counts are accumulated as integers and stored as doubles. 1 <= dim <= 512,
+ * 1 <= n_clusters <= 1024, vocab_size < 2^31. An id outside [0, vocab_size) sets DW_S_BAD_INDEX:
+ * its label is -1 and it contributes nothing to the sums, the counts or the inertia (it counts as
+ * changed when -1 differs from its previous label); nothing out of range is read. n = 0 writes
+ * nothing. Both products run on v_mfma_f64_16x16x4_f64 over tiles of 16 samples: the scores
+ * X C^T against centroid tiles of 16 streamed with a running (min, argmin), padded centroid
+ * columns taking no part, and the sums (one-hot)^T X per group of 64 clusters, each block's
+ * accumulators in registers; a dim that is no multiple of 4, a table that is not 16-B aligned
+ * and a short last tile take zero-filled operands as in dw_node_softmax. All sums float64 and
+ * reproducible bit for bit: per-block partial rows in the workspace
+ * (>= dw_kmeans_step_workspace_bytes(n, dim, n_clusters), 256-byte aligned) added in block order
+ * by a last kernel, grids that depend on (n, dim, n_clusters) only, no float atomics. */
+int dw_kmeans_step_workspace_bytes(int64_t n, int32_t dim, int32_t n_clusters, size_t *bytes);
+int dw_kmeans_step(const float *table, int64_t vocab_size, int32_t dim, const int64_t *ids,
+                   int64_t n, const double *centroids, int32_t n_clusters,
+                   const int32_t *prev_labels, int32_t *labels_out, double *out, void *workspace,
+                   size_t workspace_bytes, int32_t *status, void *stream);
+
+/* k-means++ seeding (Arthur & Vassilvitskii 2007; the plain law, not sklearn's greedy variant)
+ * over the rows table[ids[i]], n >= n_clusters. U_j = the Philox4x32-10 block of counter
+ * (j, 0, 0, 0x4B4D0000) under key (seed lo, seed hi), words x, y joined as
+ * ((x >> 5) << 26 | y >> 6) 2^-53. Centre 0 is sample floor(U_0 n). For centre j >= 1, D2[i] is
+ * the squared distance (float64, columns in ascending order) from sample i to the nearest of
+ * centres 0 .. j - 1, updated by one pass per centre, and the draw is the first sample with
+ * D2 > 0 whose running sum of D2 exceeds U_j T (T the total; the sums are hierarchical: index
+ * order inside a block of 256 samples, block order inside 256 chunks, chunk order), so sample i
+ * is drawn with probability D2[i] / T. If every remaining D2 is zero — fewer distinct rows than
+ * n_clusters — centre j is the lowest sample index not chosen yet. chosen_out int64[n_clusters]
+ * receives the sample indices (into ids), centroids_out double[n_clusters, dim] their rows
+ * widened. An id outside [0, vocab_size) sets DW_S_BAD_INDEX, has D2 = 0 and, if chosen, gives a
+ * row of zeros. Workspace >= dw_kmeans_seed_workspace_bytes(n), 256-byte aligned. Reproducible
+ * bit for bit; n = 0 writes nothing. */
+int dw_kmeans_seed_workspace_bytes(int64_t n, size_t *bytes);
+int dw_kmeans_seed(const float *table, int64_t vocab_size, int32_t dim, const int64_t *ids,
+                   int64_t n, int32_t n_clusters, uint64_t seed, int64_t *chosen_out,
+                   double *centroids_out, void *workspace, size_t workspace_bytes,
+                   int32_t *status, void *stream);
+
+/* The contingency table of two partitions: table_out int64[Ka, Kb] (zeroed here), cell [a, b] the
+ * number of i with labels_a[i] = a and labels_b[i] = b, by integer atomics. Labels int32; -1 in
+ * either array skips the sample; any other label outside its range sets DW_S_BAD_INDEX and
+ * skips it. Ka Kb <= 2^24. n = 0 writes nothing. */
+int dw_partition_counts(const int32_t *labels_a, int32_t n_a_classes, const int32_t *labels_b,
+                        int32_t n_b_classes, int64_t n, int64_t *table_out, int32_t *status,
+                        void *stream);
+
+/* The integers of the structural (unweighted) modularity of labels int32[n_rows] over a CSR
+ * graph, counted as networkx.community.modularity(G, parts, weight=None) does for the undirected
+ * graph the symmetric CSR stores: out int64[2 K] (zeroed here), [2 c] the number of CSR entries
+ * (u, v) with labels[u] = labels[v] = c and [2 c + 1] the summed degree of cluster c, a
+ * self-loop entry (stored once) counting twice in both. Q = sum_c in_c / 2m - (deg_c / 2m)^2
+ * with 2m = sum_c deg_c. A row of label -1 is skipped (its entries count for no cluster); a label
+ * outside [-1, K), a column outside [0, n_rows) or a malformed row_ptr sets DW_S_BAD_INDEX and
+ * skips the row. Weights are not read. n_rows = 0 writes nothing. */
+int dw_modularity_counts(const int64_t *row_ptr, const int32_t *col, int64_t n_rows, int64_t nnz,
+                         const int32_t *labels, int32_t n_clusters, int64_t *out, int32_t *status,
+                         void *stream);
+
 /* nn.Embedding(max_norm=...) lookup side effect (model.py:24-25 with max_norm set; torch
  * embedding_renorm_): every DISTINCT row among ids[0..n_ids) whose L2 norm exceeds max_norm is
  * scaled by max_norm / (norm + 1e-7), in place. Ids are deduplicated on the device (radix sort
